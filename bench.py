@@ -10,7 +10,12 @@ Multi-GPU: one process per GPU (torchrun), reference views sharded across ranks,
 data-path collective; the only collectives are the timing barrier and the
 max-over-ranks reduction of the elapsed time.
 
-Also reported on the same JSON line:
+A plain run (``--gpus 1 --steps N --warmup W``) sets up, warms up, times the N steps, writes
+the last step's outputs if ``--dump-outputs DIR`` is given, and prints the JSON line with the
+headline figure alone.  Everything else is measured only with ``--full`` (each leg can still be
+switched off with its ``--no-*`` option).
+
+With ``--full``, also reported on the same JSON line:
   roofline      the dominant kernel's achieved algorithmic bytes (HBM-bound) or flops
                 (MFMA-bound) per launch / its average launch time, from hipEvents
                 recorded on the launch stream over the timed region;
@@ -530,6 +535,9 @@ def train_main(args, rank: int, world: int, dev) -> None:
         loss = step()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, dev)
+    if args.dump_outputs:   # the step's loss and the gradients it left (a seeded sample if large)
+        grads = torch.cat([p.grad.reshape(-1) for p in core.parameters() if p.grad is not None])
+        dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "grads": grads}, rank, world)
     ok = bool(torch.isfinite(loss)) and all(p.grad is None or bool(torch.isfinite(p.grad).all())
                                             for p in core.parameters())
     nparam = sum(p.numel() for p in core.parameters() if p.requires_grad)
@@ -594,6 +602,31 @@ def train_main(args, rank: int, world: int, dev) -> None:
             "train_kernels": kern,
         }
         print(json.dumps(line), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(directory: str, arrays: dict, rank: int, world: int) -> None:
+    """``--dump-outputs``: write the last timed step's outputs as ``DIR/<name>.npy`` (float32;
+    ``<name>_rank<r>`` when several ranks run).  An array that would take the total past
+    DUMP_LIMIT_BYTES is stored as a fixed, seeded sample of its elements (the same indices in
+    every run, so that two builds compare element for element)."""
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, world)
+    share = budget // max(1, len(arrays)) - 4096   # room for the .npy header
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() * 4 > share:
+            n = share // 4
+            idx = np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.numel(), size=n, replace=False)
+            idx.sort()
+            a = flat[torch.from_numpy(idx).to(flat.device)].float().cpu().numpy()
+        else:
+            a = t.detach().float().cpu().numpy()
+        suffix = f"_rank{rank}" if world > 1 else ""
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def spawn_ranks(n: int) -> int:
@@ -663,7 +696,18 @@ def main():
     ap.add_argument("--planes", type=int, default=0,
                     help="profiling aid: sweep only the first P depth planes (0 = all D); "
                          "per-launch figures are unchanged, the headline value is not comparable")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: per-kernel timing and "
+                         "roofline, CPU baseline and parity, fusion, end-to-end forward, training step "
+                         "(each leg can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as "
+                         "DIR/<name>.npy (float32, at most 64 MB in all)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run measures the headline figure only
+        args.no_cpu = args.no_kernel_timing = args.no_fusion = args.no_e2e = args.no_train = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
@@ -716,6 +760,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     elapsed = max_over_ranks(elapsed, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"depth": out["depth"], "conf": out["conf"]}, rank, world)
 
     # separate kernel-timing pass over the same workload: one step with a hipEvent pair
     # around every launch and the two streams serialised (one stream), so each average is
@@ -803,6 +849,7 @@ def main():
             "steps": args.steps,
             "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3),
+            "full": args.full,
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

@@ -54,6 +54,46 @@ def test_bench_refuses_to_oversubscribe_one_gpu():
     assert r.returncode == 2, (r.returncode, r.stderr[-2000:])
 
 
+PLAIN = ["--gpus", "1", "--config", "plumbing_160x128_n3_d48", "--steps", "2", "--warmup", "1"]
+EXTRAS = ("roofline", "cpu_baseline", "parity", "fusion", "e2e", "train")
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run reports the headline figure alone (everything else needs ``--full``), and
+    ``--dump-outputs`` writes the last timed step's depth and confidence maps as float32 .npy:
+    the inputs are seeded, the sweep is deterministic, so two runs write identical arrays."""
+    import numpy as np
+    runs = []
+    for name in ("a", "b"):
+        r = _bench(PLAIN + ["--dump-outputs", str(tmp_path / name)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        runs.append(_line(r.stdout))
+    for ln in runs:
+        assert ln["full"] is False and ln["steps"] == 2 and ln["ms_per_step"] > 0
+        assert ln["unit"] == "depth-hypotheses/s" and ln["higher_is_better"] is True
+        assert all(ln[k] is None for k in EXTRAS) and ln["kernels"] == {}
+        hyp = 128 * 160 * 48
+        assert abs(ln["value"] * ln["ms_per_step"] / 1e3 - hyp) / hyp < 1e-2
+    assert sorted(p.name for p in (tmp_path / "a").iterdir()) == ["conf.npy", "depth.npy"]
+    for f in ("depth.npy", "conf.npy"):
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype == np.float32 and a.shape == (1, 128, 160)
+        assert np.isfinite(a).all() and np.array_equal(a, b)
+    d = np.load(tmp_path / "a" / "depth.npy")
+    assert 425.0 <= d.min() and d.max() <= 935.0   # the hypotheses' range
+
+
+def test_bench_full_reports_the_other_figures():
+    """``--full`` adds the kernel-timing pass (per-kernel table, roofline) and the CPU baseline
+    with its parity leg; the heavy legs are switched off here to keep the test short.  The parity bounds are smoke()'s."""
+    r = _bench(PLAIN + ["--full", "--cpu-planes", "1", "--no-fusion", "--no-e2e", "--no-train"])
+    assert r.returncode == 0, r.stderr[-3000:]
+    ln = _line(r.stdout)
+    assert ln["full"] is True and ln["kernels"] and ln["roofline"]["kernel"] in ln["kernels"]
+    assert ln["cpu_baseline"]["value"] > 0
+    assert ln["parity"]["cost_max_abs_err"] < 1e-4 and ln["parity"]["depth_rel_l1"] <= 1e-3
+
+
 TRAIN = ["--train", "--train-planes", "4", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-kernel-timing"]
 
 

@@ -1,5 +1,6 @@
 #!/bin/bash
-# The default bench line (what the driver runs at round end) into gpurun_out/$1.json
+# The complete bench line (bench.py --full, every leg) into $OUT/$1.json
+OUT=${OUT:-bench_out}   # where the logs and result lines go
 set -o pipefail
-mkdir -p gpurun_out
-timeout -k 10 1000 python bench.py > gpurun_out/$1.json 2> gpurun_out/$1.err
+mkdir -p $OUT
+timeout -k 10 1000 python bench.py --full > $OUT/$1.json 2> $OUT/$1.err
