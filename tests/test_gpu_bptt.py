@@ -169,7 +169,9 @@ def bound(name, e_cpu32):
 
 def _f32_spread(feats, proj, dv, P, R, g64):
     """{tensor: max over F32_THREADS of float32 autograd's relative L2 error vs float64};
-    keys 'features', 'x' and the parameter names.  g64 = _oracle_grads(..., float64)."""
+    keys 'features', 'x', the parameter names and, per (view, batch element) slice of the
+    feature gradient, 'features[v,b]' (an error confined to one view's slice is small in the
+    whole tensor's norm).  g64 = _oracle_grads(..., float64)."""
     _, gf64, gp64, gx64 = g64
     prev = torch.get_num_threads()
     worst = {}
@@ -181,6 +183,9 @@ def _f32_spread(feats, proj, dv, P, R, g64):
                  "x": rel_l2(np.stack([g.numpy() for g in gx32]), np.stack([g.numpy() for g in gx64]))}
             for k in gp64:
                 e[k] = rel_l2(gp32[k].numpy(), gp64[k].numpy())
+            for v in range(gf64.shape[0]):
+                for b in range(gf64.shape[1]):
+                    e[f"features[{v},{b}]"] = rel_l2(gf32[v, b].numpy(), gf64[v, b].numpy())
             for k, v in e.items():
                 worst[k] = max(worst.get(k, 0.0), v)
     finally:
