@@ -7,16 +7,16 @@
 #include <cstdint>
 
 #include "../../include/aarmvs.h"
+#include "sweep_schedule.h"
 
 namespace aarmvs {
 
 constexpr int kC = 32;          // feature channels (FeatNet output)
 constexpr int kSlots = 32;      // fp64 atomic slots per GroupNorm statistic
 constexpr float kGnEps = 1e-5f; // nn.GroupNorm default eps
-// The sweep computes cost slices in groups of up to kPlaneGroup planes: one launch of each
-// cost-slice kernel covers the group, so the neighbouring planes' bilinear footprints (and
-// the reference tile) are fetched from HBM once and re-read from L2.
-constexpr int kPlaneGroup = 16;
+// The sweep computes cost slices in groups of up to kPlaneGroup planes (sweep_schedule.h): one
+// launch of each cost-slice kernel covers the group, so the neighbouring planes' bilinear
+// footprints (and the reference tile) are fetched from HBM once and re-read from L2.
 
 // ---------------------------------------------------------------------------
 // Parameter tensors, in raw-blob order (aarmvs.h).
@@ -82,13 +82,6 @@ const ParamLayout& param_layout();
 // ---------------------------------------------------------------------------
 // Workspace layout.
 // ---------------------------------------------------------------------------
-// hidden-state ring lengths: h_k of plane e is overwritten by plane e + kHRing[k], so the
-// multi-stream regulariser's unit writing h_k may run up to kHRing[k] - 1 planes ahead of the
-// last unit that reads it (h0: cell 4, four units on; h1: cell 3; h2: deconv_0; h3: deconv_1)
-constexpr int kHRingMax = 6;
-constexpr int kHRing[5] = {6, 4, 3, 3, 2};
-inline int h_slot(int k, int e) { return e % kHRing[k]; }
-
 struct Workspace {
   double* omega_stats;    // [kPlaneGroup][B][nsrc][3][kSlots][2] omega GN statistics per group plane
   double* omega_part;     // [kPlaneGroup][B][nsrc][omega_part_n][2] per-block GN partial sums
@@ -204,7 +197,7 @@ UnetIO unet_io_record(const TrainLayout& T, const aarmvs_train_record& r, int d)
 // deconv_0 + cell 3 | deconv_1 + cell 4); a unit of plane d reads only the earlier units'
 // outputs of plane d and its own state, so the units of neighbouring planes may run at once on
 // different streams (the sweep's multi-stream regulariser)
-constexpr int kUnetUnits = 5, kUnetAll = (1 << kUnetUnits) - 1;
+constexpr int kUnetAll = (1 << kUnetUnits) - 1;
 hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom& g,
                             const Workspace& ws, const UnetIO& io, hipStream_t s,
                             int stages = kUnetAll);

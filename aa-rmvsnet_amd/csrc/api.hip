@@ -563,71 +563,24 @@ float* aarmvs_state_ptr(void* workspace, int B, int H, int W, int nsrc, int plan
 
 }  // extern "C"
 
-// Multi-stream regulariser.  The U-Net step is five units run in order (U0 cell 0, U1 cell 1,
-// U2 cell 2, U3 deconv_0 + cell 3, U4 deconv_1 + cell 4 and the head); a unit of plane d needs
-// the earlier units of plane d and its own state only, so the units of neighbouring planes can
-// run at once on different streams (stream 0 the caller's, the others library-owned).  Per unit
-// and plane an event (a ring of kRegEvRing per unit):
-//   data: a unit waits for the previous unit of its plane when that ran on another stream;
-//   slots: unit k < 4 overwrites h_k's slot of plane d - kHRing[k]; it waits for that plane's
-//   last reader of h_k when that ran on another stream (h0: U4, h1: U3, h2: U3, h3: U4; h4 is
-//   read by U4's own head).  The other readers of the slot finished before the last one (the
-//   data waits chain a plane's units).  c_k, u0, u1, the deconv partials and the WTA images
-//   each have one unit as their only reader and writer.
-// Bit-identical to one stream (the same kernels on the same inputs).
-// How many streams: a process gets GPU_MAX_HW_QUEUES = 4 hardware queues here, and streams
-// beyond that share them (a stream waiting on an event then blocks the other's work), so a
-// sweep uses at most four: with an aux stream (the caller asks for concurrency), the cost stage
-// on it and the units on three (the caller's + two library streams: cells 0-1 | cell 2,
-// deconv_0, cell 3 | deconv_1, cell 4, head).  Small frames (B*H*W <= kSmallFramePx) instead
-// put the cost stage on the caller's stream beside cells 0-1 and the other units on the aux
-// stream and two library streams (cell 2 | deconv_0, cell 3 | deconv_1, cell 4, head), still
-// four streams (the library's are shared with the backward, library_stream): their kernels are a few
-// microseconds of one or two tiles per block, so the chain's latency, not the cost stage, is
-// what overlapping hides (config 1: 0.279 -> 0.334 G hyp/s, profiles/r06o_small_frames.txt).
-// Overrides (A/B runs): AARMVS_REG_STREAMS=1..5 the unit stream count (AARMVS_REG_STREAMS_REC for
-// a training forward), AARMVS_REG_MAP five digits unit -> stream (unit 0 on stream 0),
-// AARMVS_SMALL_PX the small-frame threshold.
-constexpr int kRegMaxStreams = 5, kRegEvRing = 8;
-static_assert(kRegMaxStreams - 1 <= kLibStreams, "the unit streams beyond the caller's are library streams");
-static_assert(kRegEvRing > kHRingMax, "a unit's event is re-recorded only after its waiters are enqueued");
-constexpr int kHLastReader[4] = {4, 3, 3, 4};
-constexpr long kSmallFramePx = 65536;
-static bool small_frame(long px) {
-  const char* s = std::getenv("AARMVS_SMALL_PX");
-  return px <= ((s && *s) ? std::atol(s) : kSmallFramePx);
-}
-static int reg_streams(bool aux, bool rec, bool small) {
-  const char* s = std::getenv(rec ? "AARMVS_REG_STREAMS_REC" : "AARMVS_REG_STREAMS");
-  const int n = (s && *s) ? std::atoi(s) : (!aux ? 1 : small ? 4 : 3);
-  return std::max(1, std::min(kRegMaxStreams, n));
-}
-// the stream of each unit for n streams; returns the number of streams used
-static int reg_unit_streams(int n, int (&us)[kUnetUnits]) {
-  static const int map[kRegMaxStreams][kUnetUnits] = {
-      {0, 0, 0, 0, 0}, {0, 0, 0, 1, 1}, {0, 0, 1, 1, 2}, {0, 0, 1, 2, 3}, {0, 1, 2, 3, 4}};
-  for (int i = 0; i < kUnetUnits; ++i) us[i] = map[n - 1][i];
-  const char* m = n > 1 ? std::getenv("AARMVS_REG_MAP") : nullptr;
-  if (m && std::strlen(m) == kUnetUnits && m[0] == '0') {
-    int top = 0;
-    bool ok = true;
-    for (int i = 0; i < kUnetUnits; ++i) {
-      ok = ok && m[i] >= '0' && m[i] < '0' + kRegMaxStreams;
-      top = std::max(top, m[i] - '0');
-    }
-    if (ok) {
-      for (int i = 0; i < kUnetUnits; ++i) us[i] = m[i] - '0';
-      return top + 1;
-    }
-  }
-  return n;
-}
-
-// planes per cost-stage group: kPlaneGroup, or AARMVS_NPL=n (1 <= n <= kPlaneGroup; A/B runs)
-static int plane_group() {
-  const char* s = std::getenv("AARMVS_NPL");
-  const int n = (s && *s) ? std::atoi(s) : kPlaneGroup;
-  return std::max(1, std::min(kPlaneGroup, n));
+// The sweep's stream schedule is sweep_schedule.h: plan_sweep chooses the streams, walk_sweep
+// gives the order of the launches, records and waits, aarmvs_sweep executes them.
+static_assert(kLib4 - kLib1 + 1 == kLibStreams && kRegMaxStreams - 1 == kLibStreams,
+              "unit streams 1..3 are library streams 1..3; a fifth unit stream is library stream "
+              "4, the stream aarmvs_aux_stream returns");
+// the overrides of a call (read per call: A/B runs switch them within one process)
+static SweepOverrides sweep_overrides() {
+  auto opt = [](const char* name) {
+    const char* s = std::getenv(name);
+    return (s && *s) ? SweepOpt{true, std::atol(s)} : SweepOpt{};
+  };
+  SweepOverrides o;
+  o.reg_streams = opt("AARMVS_REG_STREAMS");
+  o.reg_streams_rec = opt("AARMVS_REG_STREAMS_REC");
+  o.small_px = opt("AARMVS_SMALL_PX");
+  o.npl = opt("AARMVS_NPL");
+  o.reg_map = std::getenv("AARMVS_REG_MAP");
+  return o;
 }
 
 hipError_t aarmvs::library_stream(int dev, int i, hipStream_t& out) {
@@ -645,6 +598,93 @@ hipError_t aarmvs::library_stream(int dev, int i, hipStream_t& out) {
   out = pool[dev][i];
   return hipSuccess;
 }
+
+// walk_sweep's sink: one sweep call's launches, event records and event waits on HIP
+struct HipSweep {
+  const aarmvs_sweep_args* a;
+  const TrainLayout& T;
+  const SweepGeom& g;
+  const Workspace& ws;
+  const CostArgs& ca;
+  hipEvent_t* ev;
+  hipStream_t st[kSweepSlots];
+  int rc = 0, io_d = -1;
+  UnetIO io_{};
+
+  // the call's error is its first failure (the joins still run after one)
+  int check(hipError_t e, const char* where) {
+    if (e == hipSuccess) return 0;
+    if (!rc) rc = hip_fail(e, where);
+    return rc;
+  }
+  // the group's cost slices: two alternating workspace slots, or the record's planes
+  float* slices(const SweepGroup& grp) const {
+    return a->record ? a->record->x + (size_t)grp.g0 * T.x_plane : ws.xg[grp.gi & 1];
+  }
+  const float* slice(const SweepGroup& grp, int d) const {
+    return slices(grp) + (size_t)(d - grp.g0) * ws.x_plane;
+  }
+  // plane d's tensors (kept from one unit of the plane to the next); own: the unit stores its
+  // statistics, never accumulates them (one writer each)
+  const UnetIO& io(int d, bool own) {
+    if (d != io_d) io_ = a->record ? unet_io_record(T, *a->record, d) : unet_io_ws(ws, d);
+    io_d = d;
+    io_.clear_stats = !own && !a->record;
+    return io_;
+  }
+
+  int fork(int slot, int i) {
+    hipError_t e = hipEventRecord(ev[i], st[0]);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st[slot], ev[i], 0);
+    return check(e, "sweep: fork");
+  }
+  int join(int slot, int i) {
+    if (st[slot] == st[0]) return 0;
+    hipError_t e = hipEventRecord(ev[i], st[slot]);
+    if (e == hipSuccess) e = hipStreamWaitEvent(st[0], ev[i], 0);
+    return check(e, "sweep: join");
+  }
+  int wait(int slot, int i) { return check(hipStreamWaitEvent(st[slot], ev[i], 0), "sweep: event wait"); }
+  int record(int slot, int i) { return check(hipEventRecord(ev[i], st[slot]), "sweep: event record"); }
+  int cost_group(int slot, const SweepGroup& grp) {
+    const aarmvs_train_record* rec = a->record;
+    // training: the group's omega conv output and statistics go straight to the record (the
+    // backward reads them instead of recomputing the omega conv; the record's per-plane layout
+    // is the workspace slots')
+    Workspace wsg = ws;
+    if (rec) {
+      wsg.t1 = rec->t1 + (size_t)grp.g0 * ws.t1_plane * 4;
+      wsg.omega_stats = rec->ostats + (size_t)grp.g0 * (ws.omega_stats_bytes / 8);
+    }
+    if (int r = check(launch_omega_group(ca, g, wsg, grp.g0, grp.n, st[slot], rec != nullptr), "sweep: omega stage"))
+      return r;
+    const int d_last = a->d_end - 1, ok = d_last < grp.g0 + grp.n ? d_last - grp.g0 : -1;
+    return check(launch_cost_x_group(ca, g, wsg, grp.g0, grp.n, slices(grp), ok >= 0 ? a->omega_out : nullptr,
+                                     ok, st[slot]),
+                 "sweep: cost slices");
+  }
+  int slice_copy(const SweepGroup& grp, int d) {
+    return check(launch_layout(slice(grp, d), a->slice_out, a->B, kC, a->H * a->W, false, st[0]),
+                 "sweep: slice copy");
+  }
+  int step(const SweepGroup& grp, int d) {
+    const UnetIO& all = io(d, false);
+    if (int r = check(launch_unet_step(slice(grp, d), ca.params, g, ws, all, st[0]), "sweep: regulariser step"))
+      return r;
+    return head_on(st[0], all, d);
+  }
+  int unit(int slot, int u, const SweepGroup& grp, int d) {
+    return check(launch_unet_step(slice(grp, d), ca.params, g, ws, io(d, true), st[slot], 1 << u),
+                 "sweep: regulariser step");
+  }
+  int head(int slot, int d) { return head_on(st[slot], io(d, true), d); }
+  // the WTA images are maintained on every plane, whether or not this call returns depth:
+  // a sweep split into d_range calls gives the same depth/confidence however its earlier
+  // pieces were requested (24 B/px per plane, <0.5% of a plane's time)
+  int head_on(hipStream_t s, const UnetIO& io, int d) {
+    return check(launch_head_wta(ca.params, g, io, ws, a->depth_values, d, a->cost_out, true, s), "sweep: head/wta");
+  }
+};
 
 extern "C" {
 
@@ -674,194 +714,69 @@ int aarmvs_sweep(const aarmvs_sweep_args* a, hipStream_t stream) {
   ca.rel = a->rel_proj;
   ca.depth_values = a->depth_values;
   ca.params = params;
-  // Planes are processed in groups of up to kPlaneGroup (AARMVS_NPL=n for A/B runs).  The
-  // cost slices do not depend on the recurrence, so a group's whole cost-slice stage
-  // (omega conv, statistics, cost_x: one launch each over the group's planes) runs ahead of
-  // its regulariser steps.  Two-stream schedule (a->aux_stream): the cost stage runs on the
-  // aux stream, group i's beside group i-1's regulariser steps on the main stream; per
-  // group parity two events: ev_cost[p] "group's slices ready" (aux -> main) and
-  // ev_used[p] "group's slices consumed" (main -> aux, before group i+2 reuses the slots).
-  hipStream_t aux = (a->aux_stream && a->aux_stream != stream) ? a->aux_stream : nullptr;
-  // (a training forward, with its record: AARMVS_REG_STREAMS_REC; 3 streams by default too,
-  // config-4 training step 251.4 -> 243.3 ms, profiles/r06m_train_streams.txt)
-  // under stream capture (a caller recording the sweep into a graph) everything stays on
-  // `stream`: the captured graph is the one-stream order, bit-identical to every schedule
+  // under stream capture (a caller recording the sweep into a graph) everything stays on `stream`
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   if ((e = hipStreamIsCapturing(stream, &cap)) != hipSuccess) return hip_fail(e, "sweep: capture status");
-  if (cap != hipStreamCaptureStatusNone) aux = nullptr;
-  const bool small = aux && small_frame((long)a->B * a->H * a->W);
-  int ustream[kUnetUnits];
-  const int nreg = cap != hipStreamCaptureStatusNone
-                       ? reg_unit_streams(1, ustream)
-                       : reg_unit_streams(reg_streams(aux != nullptr, rec != nullptr, small), ustream);
-  // small frames: the cost stage on the caller's stream, the aux stream one of the units' streams
-  hipStream_t unit_aux = nullptr;
-  if (small && nreg > 3) {
-    unit_aux = aux;
-    aux = nullptr;
-  }
-  const int G = plane_group();
-  // ev_cost[2], ev_used[2], fork/join, and the regulariser's part events, fork/join events and
-  // streams: a per-thread, per-device set reused across calls (a sweep split into d_range
+  const SweepPlan plan =
+      plan_sweep(a->aux_stream && a->aux_stream != stream, cap != hipStreamCaptureStatusNone, rec != nullptr,
+                 (long)a->B * a->H * a->W, sweep_overrides());
+  // The events: a per-thread, per-device set reused across calls (a sweep split into d_range
   // pieces makes one call per piece).  Events are only recorded/waited on the caller's streams and the set's
   // own, and a record overwrites the previous one, so reuse is safe.
   struct EventSet {
     int dev = -1;
-    hipEvent_t ev[5 + kUnetUnits * kRegEvRing + kRegMaxStreams] = {};
+    hipEvent_t ev[kSweepEvents] = {};
   };
   static thread_local EventSet evs_dev[kMaxDevices];   // one set per device
-  auto sweep_fail = [&](hipError_t err, const char* where) { return hip_fail(err, where); };
   int dev = 0;
-  if ((e = current_device(dev)) != hipSuccess) return sweep_fail(e, "sweep: get device");
+  if ((e = current_device(dev)) != hipSuccess) return hip_fail(e, "sweep: get device");
   EventSet& evs = evs_dev[dev];
-  hipEvent_t* ev = evs.ev;
-  if ((aux || unit_aux || nreg > 1) && evs.dev != dev) {
+  if (plan.events() && evs.dev != dev) {
     for (hipEvent_t& x : evs.ev)
       if ((e = hipEventCreateWithFlags(&x, hipEventDisableTiming)) != hipSuccess)
-        return sweep_fail(e, "sweep: event create");
+        return hip_fail(e, "sweep: event create");
     evs.dev = dev;
   }
-  hipEvent_t* ev_cost = ev;
-  hipEvent_t* ev_used = ev + 2;
-  hipEvent_t(*ev_part)[kRegEvRing] = reinterpret_cast<hipEvent_t(*)[kRegEvRing]>(ev + 5);
-  hipEvent_t* ev_regjoin = ev + 5 + kUnetUnits * kRegEvRing;
-  hipStream_t rs[kRegMaxStreams] = {stream};
-  for (int i = 1, li = 1; i < nreg; ++i) {
-    if (i == 1 && unit_aux) {
-      rs[1] = unit_aux;
-      continue;
-    }
-    if ((e = library_stream(dev, li++, rs[i])) != hipSuccess) return sweep_fail(e, "sweep: stream create");
+  HipSweep run{a, T, g, ws, ca, evs.ev, {}};
+  for (int i = 0; i < kSweepSlots; ++i) {
+    const SweepStream id = plan.slot[i];
+    if (id == kCaller) run.st[i] = stream;
+    if (id == kCallerAux) run.st[i] = a->aux_stream;
+    if (id >= kLib1 && (e = library_stream(dev, id - kLib1 + 1, run.st[i])) != hipSuccess)
+      return hip_fail(e, "sweep: stream create");
   }
-  hipStream_t cs = aux ? aux : stream;   // the cost stage's stream
 
   if (a->d_begin == 0) {
     // UNetConvLSTM._init_hidden (drmvsnet.py:133-134, 202-206) and the WTA images
     // (drmvsnet.py:302-304)
     if ((e = hipMemsetAsync(ws.state_begin, 0, ws.state_bytes, stream)) != hipSuccess)
-      return sweep_fail(e, "sweep: state init");
+      return hip_fail(e, "sweep: state init");
     if ((e = hipMemsetAsync(ws.max_prob, 0, ws.wta_bytes, stream)) != hipSuccess)
-      return sweep_fail(e, "sweep: wta init");
+      return hip_fail(e, "sweep: wta init");
     if ((e = hipMemsetAsync(ws.omega_stats, 0, ws.stats_bytes, stream)) != hipSuccess)
-      return sweep_fail(e, "sweep: stats init");
+      return hip_fail(e, "sweep: stats init");
     if (rec && (e = hipMemsetAsync(rec->state, 0, T.state_slab * sizeof(float), stream)) != hipSuccess)
-      return sweep_fail(e, "sweep: record state init");
+      return hip_fail(e, "sweep: record state init");
     // c8 copies of the features for the cost stage
     const int HW = a->H * a->W;
     // (each copy also folds 8 max|feature|^2 into ws.xbound: cell 0's fp16 range guard)
     if ((e = launch_to_c8(a->ref_fea, ws.feat8[0], a->B, HW, stream, ws.xbound)) != hipSuccess)
-      return sweep_fail(e, "sweep: c8 copy");
+      return hip_fail(e, "sweep: c8 copy");
     for (int v = 0; v < a->nsrc; ++v)
       if ((e = launch_to_c8(a->src_fea[v], ws.feat8[1 + v], a->B, HW, stream, ws.xbound)) !=
           hipSuccess)
-        return sweep_fail(e, "sweep: c8 copy");
+        return hip_fail(e, "sweep: c8 copy");
   }
   // a record's statistics slabs accumulate from zero (block 0 of cells 3 and 4 fills slot 0 of each)
   if (rec && (e = hipMemsetAsync(rec->stats + (size_t)a->d_begin * T.stats_slab, 0,
                                  (size_t)(a->d_end - a->d_begin) * T.stats_slab * sizeof(double),
                                  stream)) != hipSuccess)
-    return sweep_fail(e, "sweep: record stats init");
-  if (aux) {   // fork: the aux stream starts after everything enqueued on `stream` so far
-    if ((e = hipEventRecord(ev[4], stream)) != hipSuccess ||
-        (e = hipStreamWaitEvent(aux, ev[4], 0)) != hipSuccess)
-      return sweep_fail(e, "sweep: fork");
-  }
-  // fork: the regulariser's own streams start after `stream`'s work so far
-  for (int i = 1; i < nreg; ++i)
-    if ((e = hipEventRecord(ev_regjoin[i], stream)) != hipSuccess ||
-        (e = hipStreamWaitEvent(rs[i], ev_regjoin[i], 0)) != hipSuccess)
-      return sweep_fail(e, "sweep: fork");
-  // every return from here on (errors included) leaves the aux and regulariser streams' work
-  // ordered on `stream`
-  StreamJoin join{stream, aux, ev[4]};
-  StreamJoin join_r[kRegMaxStreams] = {{stream, nullptr, nullptr},
-                                       {stream, rs[1], ev_regjoin[1]},
-                                       {stream, rs[2], ev_regjoin[2]},
-                                       {stream, rs[3], ev_regjoin[3]},
-                                       {stream, rs[4], ev_regjoin[4]}};
-  // the WTA images are maintained on every plane, whether or not this call returns depth:
-  // a sweep split into d_range calls gives the same depth/confidence however its earlier
-  // pieces were requested (24 B/px per plane, <0.5% of a plane's time)
-  const bool wta = true;
-  const int d_last = a->d_end - 1;
-  int gi = 0;
-  for (int g0 = a->d_begin; g0 < a->d_end; g0 += G, ++gi) {
-    const int n = std::min(G, a->d_end - g0);
-    // the group's cost slices: two alternating workspace slots, or the record's planes
-    float* const xs = rec ? rec->x + (size_t)g0 * T.x_plane : ws.xg[gi & 1];
-    // cost stage: its slots were last read by group gi - 2's regulariser steps
-    if (aux && gi >= 2 && (e = hipStreamWaitEvent(aux, ev_used[gi & 1], 0)) != hipSuccess)
-      return sweep_fail(e, "sweep: event wait");
-    // training: the group's omega conv output and statistics go straight to the record (the
-    // backward reads them instead of recomputing the omega conv; the record's per-plane layout
-    // is the workspace slots')
-    Workspace wsg = ws;
-    if (rec) {
-      wsg.t1 = rec->t1 + (size_t)g0 * ws.t1_plane * 4;
-      wsg.omega_stats = rec->ostats + (size_t)g0 * (ws.omega_stats_bytes / 8);
-    }
-    if ((e = launch_omega_group(ca, g, wsg, g0, n, cs, rec != nullptr)) != hipSuccess)
-      return sweep_fail(e, "sweep: omega stage");
-    const int ok = d_last < g0 + n ? d_last - g0 : -1;
-    if ((e = launch_cost_x_group(ca, g, wsg, g0, n, xs, ok >= 0 ? a->omega_out : nullptr, ok, cs)) !=
-        hipSuccess)
-      return sweep_fail(e, "sweep: cost slices");
-    if (aux && ((e = hipEventRecord(ev_cost[gi & 1], aux)) != hipSuccess ||
-                (e = hipStreamWaitEvent(stream, ev_cost[gi & 1], 0)) != hipSuccess))
-      return sweep_fail(e, "sweep: event");
-    // regulariser steps and WTA of the group's planes
-    for (int k = 0; k < n; ++k) {
-      const int d = g0 + k;
-      const float* xd = xs + (size_t)k * ws.x_plane;
-      const UnetIO io = rec ? unet_io_record(T, *rec, d) : unet_io_ws(ws, d);
-      if (d == d_last && a->slice_out) {
-        e = launch_layout(xd, a->slice_out, a->B, kC, a->H * a->W, false, stream);
-        if (e != hipSuccess) return sweep_fail(e, "sweep: slice copy");
-      }
-      if (nreg > 1) {
-        // wait for unit q of plane e on another stream (planes before this call: joined)
-        auto wait_unit = [&](int u, int q, int e) -> hipError_t {
-          if (e < a->d_begin || ustream[q] == ustream[u]) return hipSuccess;
-          return hipStreamWaitEvent(rs[ustream[u]], ev_part[q][e % kRegEvRing], 0);
-        };
-        UnetIO iom = io;
-        iom.clear_stats = false;   // the statistics are stored, never accumulated (one writer each)
-        for (int u = 0; u < kUnetUnits; ++u) {
-          hipStream_t su = rs[ustream[u]];
-          if (u > 0 && (e = wait_unit(u, u - 1, d)) != hipSuccess) return sweep_fail(e, "sweep: event wait");
-          // the hidden-state slot this unit overwrites, last read kHRing planes back
-          if (u < 4 && (e = wait_unit(u, kHLastReader[u], d - kHRing[u])) != hipSuccess)
-            return sweep_fail(e, "sweep: event wait");
-          if ((e = launch_unet_step(xd, params, g, ws, iom, su, 1 << u)) != hipSuccess)
-            return sweep_fail(e, "sweep: regulariser step");
-          if (u == kUnetUnits - 1 &&
-              (e = launch_head_wta(params, g, iom, ws, a->depth_values, d, a->cost_out, wta, su)) != hipSuccess)
-            return sweep_fail(e, "sweep: head/wta");
-          if ((e = hipEventRecord(ev_part[u][d % kRegEvRing], su)) != hipSuccess)
-            return sweep_fail(e, "sweep: event record");
-        }
-        continue;
-      }
-      if ((e = launch_unet_step(xd, params, g, ws, io, stream)) != hipSuccess)
-        return sweep_fail(e, "sweep: regulariser step");
-      if ((e = launch_head_wta(params, g, io, ws, a->depth_values, d, a->cost_out, wta,
-                               stream)) != hipSuccess)
-        return sweep_fail(e, "sweep: head/wta");
-    }
-    if (aux && (e = hipEventRecord(ev_used[gi & 1], stream)) != hipSuccess)
-      return sweep_fail(e, "sweep: event record");
-  }
-  if (aux) {   // join: everything the call enqueued is ordered on `stream` at return
-    join.aux = nullptr;
-    if ((e = hipEventRecord(ev[4], aux)) != hipSuccess ||
-        (e = hipStreamWaitEvent(stream, ev[4], 0)) != hipSuccess)
-      return sweep_fail(e, "sweep: join");
-  }
-  for (int i = 1; i < nreg; ++i)
-    if ((e = join_r[i].join()) != hipSuccess) return sweep_fail(e, "sweep: join");
+    return hip_fail(e, "sweep: record stats init");
+  // forks, the groups' cost stages and regulariser steps, joins (sweep_schedule.h)
+  if ((rc = walk_sweep(plan, a->d_begin, a->d_end, a->slice_out ? a->d_end - 1 : -1, run))) return rc;
   if ((a->depth_out || a->conf_out) && a->d_end == a->D) {
     if ((e = launch_finalize(g, ws, a->depth_out, a->conf_out, stream)) != hipSuccess)
-      return sweep_fail(e, "sweep: finalize");
+      return hip_fail(e, "sweep: finalize");
   }
   return AARMVS_OK;
 }

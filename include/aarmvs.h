@@ -201,8 +201,11 @@ int aarmvs_sweep_backward(const aarmvs_backward_args* args, hipStream_t stream);
 
 /* Hidden state of the regulariser inside the workspace, for inspection/BPTT:
  * cell k in 0..4, which = 0 for h, 1 for c, planes = the number of planes (or
- * aarmvs_unet_step steps) processed so far: the state they left (h lives in a ring of
- * 3 slots for cell 0 and 2 for the others, indexed by plane).  Valid after an
+ * aarmvs_unet_step steps) processed so far: the state they left (h lives in a per-cell
+ * ring indexed by planes % kHRing[k]: 6, 4, 3, 3 and 2 slots for h0..h4, so that the units of
+ * neighbouring planes can run on separate streams.  The rings are part of
+ * aarmvs_sweep_workspace_bytes: 572 B per pixel against 264 B for two slots each; at
+ * 1600x1184 and B = 1, h0 alone takes about 485 MB more).  Valid after an
  * aarmvs_sweep call; returns a device pointer to [B,H_k,W_k,hid_k] (NHWC: the workspace
  * keeps the U-Net tensors channel-innermost) or NULL. */
 float* aarmvs_state_ptr(void* workspace, int B, int H, int W, int nsrc, int planes,
