@@ -88,6 +88,22 @@ class FusionArgs(ctypes.Structure):
     ]
 
 
+class FusionPointsArgs(ctypes.Structure):
+    """Mirror of ``aarmvs_fusion_points_args``."""
+    _fields_ = [
+        ("H", c_int), ("W", c_int),
+        ("mask", c_void_p),
+        ("depth", c_void_p),
+        ("color", c_void_p),
+        ("cams", c_void_p),
+        ("xyz", c_void_p),
+        ("rgb", c_void_p),
+        ("capacity", ctypes.c_longlong),
+        ("count", c_void_p),
+        ("workspace", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "aarmvs_last_error": (c_char_p, []),
@@ -126,6 +142,9 @@ SIGNATURES = {
     "aarmvs_wta_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   c_void_p]),
     "aarmvs_fusion_filter": (c_int, [ctypes.POINTER(FusionArgs), c_void_p]),
+    "aarmvs_pyr_down": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "aarmvs_fusion_points_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "aarmvs_fusion_points": (c_int, [ctypes.POINTER(FusionPointsArgs), c_void_p]),
     "aarmvs_evidential_epilogue": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p,
                                            c_void_p, c_void_p]),
     "aarmvs_evidential_epilogue_backward": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int,

@@ -12,6 +12,12 @@ read/write the formats the fusion step consumes: PFM maps (``datasets.data_io``,
 reference's datasets/data_io.py:9-74, re-exported here), cam files (fusion.py:27-42), pair files (fusion.py:57-68), images (fusion.py:45-50), masks
 (fusion.py:52-56) and a binary PLY writer for the point cloud.
 Depth maps must be CUDA float32 tensors; there is no CPU fallback.
+
+Tanks and Temples goes through the reference's fusion_padding.py instead: ``filter_depth_tnt``
+is that per-scan driver (halved intrinsics, rows [2:-2] of the maps, ``pyr_down`` of the image
+(``aarmvs_pyr_down``), the same filter core, and ``fuse_points_gpu`` (``aarmvs_fusion_points``)
+for the kept pixels' points).  ``python -m aarmvs.fusion --test_dataset {dtu,tnt} ...`` runs
+either driver over a scan list.
 """
 from __future__ import annotations
 
@@ -202,6 +208,159 @@ def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="
 
 
 # ---------------------------------------------------------------------------------
+# Tanks and Temples (the reference's fusion_padding.py)
+# ---------------------------------------------------------------------------------
+def pyr_down(img: torch.Tensor) -> torch.Tensor:
+    """cv2.pyrDown(img) of a CUDA float32 [H,W] or [H,W,3] image (fusion_padding.py:166):
+    [(H+1)//2, (W+1)//2(, 3)], one ``aarmvs_pyr_down`` launch.  OpenCV's scalar float path
+    (imgproc/src/pyramids.cpp) restated op for op; cv2 is not installed here and its SIMD paths
+    may associate the sums differently, so agreement with cv2 itself is parity unpinned."""
+    if not (isinstance(img, torch.Tensor) and img.is_cuda and img.dtype == torch.float32):
+        raise AarmvsError("aarmvs: pyr_down needs a CUDA float32 tensor")
+    if not (img.dim() == 2 or (img.dim() == 3 and img.shape[2] == 3)):
+        raise AarmvsError(f"aarmvs: pyr_down needs an [H,W] or [H,W,3] image, got {tuple(img.shape)}")
+    img = img.contiguous()
+    H, W = img.shape[:2]
+    out = torch.empty(((H + 1) // 2, (W + 1) // 2) + tuple(img.shape[2:]), dtype=torch.float32,
+                      device=img.device)
+    with torch.cuda.device(img.device):
+        check(lib().aarmvs_pyr_down(img.data_ptr(), H, W, 1 if img.dim() == 2 else 3, out.data_ptr(),
+                                    torch.cuda.current_stream().cuda_stream), "pyr_down")
+    return out
+
+
+def pack_point_cameras(ref_cam) -> np.ndarray:
+    """inv(K) 3x3 then inv(E) 4x4 as numpy forms them in float32 (fusion_padding.py:246-249),
+    packed for ``aarmvs_fusion_points``."""
+    K, E = (np.asarray(m, np.float32) for m in ref_cam)
+    return np.ascontiguousarray(np.concatenate([np.linalg.inv(K).ravel(), np.linalg.inv(E).ravel()])
+                                .astype(np.float32))
+
+
+def fuse_points_into(depth_avg, final_mask, ref_cam, ref_img, xyz, rgb) -> torch.Tensor:
+    """The kept pixels' world points into the caller's buffers: xyz float32 [capacity,3], rgb
+    uint8 [capacity,3] (None if and only if ref_img is), in pixel order; points past the
+    capacity are dropped.  Returns the number of kept pixels as a CUDA int64 [1] tensor,
+    without waiting for the device."""
+    if not (isinstance(depth_avg, torch.Tensor) and depth_avg.is_cuda and depth_avg.dtype == torch.float64
+            and depth_avg.dim() == 2):
+        raise AarmvsError("aarmvs: fuse_points_gpu needs the averaged depth as a CUDA float64 [H,W] tensor")
+    dev = depth_avg.device
+    if not (isinstance(final_mask, torch.Tensor) and final_mask.device == dev
+            and final_mask.dtype in (torch.bool, torch.uint8) and final_mask.shape == depth_avg.shape):
+        raise AarmvsError("aarmvs: fuse_points_gpu needs the mask as a CUDA bool / uint8 [H,W] tensor "
+                          "of the depth map's size")
+    H, W = depth_avg.shape
+    if (ref_img is None) != (rgb is None):
+        raise AarmvsError("aarmvs: fuse_points_gpu: colours out need an image, and an image colours out")
+    if ref_img is not None:
+        if not (isinstance(ref_img, torch.Tensor) and ref_img.device == dev and ref_img.dtype == torch.float32):
+            raise AarmvsError("aarmvs: fuse_points_gpu needs the image as a CUDA float32 tensor")
+        if tuple(ref_img.shape) != (H, W, 3):
+            raise AarmvsError(f"aarmvs: image {tuple(ref_img.shape[:2])} and depth map {(H, W)} differ in size")
+        ref_img = ref_img.contiguous()
+    for t, dt, what in ((xyz, torch.float32, "xyz"), (rgb, torch.uint8, "rgb")):
+        if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt
+                                  and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous()):
+            raise AarmvsError(f"aarmvs: fuse_points_gpu: {what} must be a contiguous CUDA [n,3] tensor")
+    if rgb is not None and rgb.shape[0] != xyz.shape[0]:
+        raise AarmvsError("aarmvs: fuse_points_gpu: xyz and rgb differ in capacity")
+    depth_avg, final_mask = depth_avg.contiguous(), final_mask.contiguous()
+    cams = pack_point_cameras(ref_cam)
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    work = torch.empty(max(1, lib().aarmvs_fusion_points_workspace_bytes(H, W)), dtype=torch.uint8, device=dev)
+    a = _lib.FusionPointsArgs()
+    a.H, a.W = H, W
+    a.mask, a.depth = final_mask.data_ptr(), depth_avg.data_ptr()
+    a.color = None if ref_img is None else ref_img.data_ptr()
+    a.cams = cams.ctypes.data
+    a.xyz = xyz.data_ptr()
+    a.rgb = None if rgb is None else rgb.data_ptr()
+    a.capacity = xyz.shape[0]
+    a.count, a.workspace = count.data_ptr(), work.data_ptr()
+    with torch.cuda.device(dev):
+        check(lib().aarmvs_fusion_points(ctypes.byref(a), torch.cuda.current_stream().cuda_stream),
+              "fusion_points")
+    return count
+
+
+def fuse_points_gpu(depth_avg, final_mask, ref_cam, ref_img=None):
+    """``fuse_points`` on the GPU (``aarmvs_fusion_points``): CUDA float64 averaged depth, CUDA
+    bool mask and (optionally) a CUDA float32 [H,W,3] image in, (xyz float32 [n,3], rgb uint8
+    [n,3] or None) out as CUDA tensors, the points in pixel order and bit-equal to numpy's."""
+    if not (isinstance(depth_avg, torch.Tensor) and depth_avg.is_cuda and depth_avg.dim() == 2):
+        raise AarmvsError("aarmvs: fuse_points_gpu needs the averaged depth as a CUDA float64 [H,W] tensor")
+    (H, W), dev = depth_avg.shape, depth_avg.device
+    xyz = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
+    rgb = None if ref_img is None else torch.empty(H * W, 3, dtype=torch.uint8, device=dev)
+    n = int(fuse_points_into(depth_avg, final_mask, ref_cam, ref_img, xyz, rgb).item())
+    return xyz[:n], (None if rgb is None else rgb[:n])
+
+
+def read_camera_parameters_tnt(filename):
+    """(intrinsics float32 3x3, extrinsics float32 4x4) of a cam.txt with intrinsics rows 0
+    and 1 halved in float32 (fusion_padding.py:29-39: the maps are half the image's size)."""
+    intrinsics, extrinsics = read_camera_parameters(filename)
+    intrinsics[:2] /= 2
+    return intrinsics, extrinsics
+
+
+def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, device="cuda"):
+    """fusion_padding.py:137-266 for one scan.  Per reference view of pair.txt: the image goes
+    to the GPU and through ``pyr_down``; rows [2:-2] are cropped from the reference and source
+    depth maps and the confidence map (the padding loader's extra rows); ``filter_depth_core``
+    runs with the halved cameras (with up to 10 source views its vote rule is
+    fusion_padding.py's fixed one); ``fuse_points_gpu`` extracts the kept
+    points.  Only the three masks (for the PNGs under out_folder/mask) and the kept points come
+    back to the host.  Writes plyfilename and returns the number of points.  A reference view
+    without a depth map is skipped (the reference stops with an error there)."""
+    vertexs, vertex_colors = [], []
+    dev = torch.device(device)
+    cam_file = os.path.join(scan_folder, "cams/{:0>8}_cam.txt")
+    depth_file = os.path.join(out_folder, "depth_est_0/{:0>8}.pfm")
+    cache = {}
+
+    def cropped(path):
+        return torch.from_numpy(np.ascontiguousarray(read_pfm(path)[0])).to(dev)[2:-2]
+
+    def depth_of(view):
+        if view not in cache:
+            cache[view] = cropped(depth_file.format(view))
+        return cache[view]
+
+    for ref_view, src_views in read_pair_file(os.path.join(scan_folder, "pair.txt")):
+        if not os.path.exists(depth_file.format(ref_view)):
+            print("skip", ref_view)
+            continue
+        ref_cam = read_camera_parameters_tnt(cam_file.format(ref_view))
+        ref_img = pyr_down(torch.from_numpy(
+            read_img(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref_view)))).to(dev))
+        ref_depth_est = depth_of(ref_view)
+        confidence = cropped(os.path.join(out_folder, "confidence_0/{:0>8}.pfm".format(ref_view)))
+        if tuple(ref_img.shape[:2]) != tuple(ref_depth_est.shape):
+            raise AarmvsError(f"aarmvs: view {ref_view}: the halved image is {tuple(ref_img.shape[:2])} "
+                              f"but the cropped depth map is {tuple(ref_depth_est.shape)}")
+        src_cams = [read_camera_parameters_tnt(cam_file.format(v)) for v in src_views]
+        photo, geo, final, avg = filter_depth_core(ref_depth_est, confidence, ref_cam,
+                                                   [depth_of(v) for v in src_views], src_cams, photo_threshold)
+        xyz, rgb = fuse_points_gpu(avg, final, ref_cam, ref_img)
+        photo, geo, final = (m.cpu().numpy() for m in (photo, geo, final))
+        os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
+        save_mask(os.path.join(out_folder, "mask/{:0>8}_photo.png".format(ref_view)), photo)
+        save_mask(os.path.join(out_folder, "mask/{:0>8}_geo.png".format(ref_view)), geo)
+        save_mask(os.path.join(out_folder, "mask/{:0>8}_final.png".format(ref_view)), final)
+        print("processing {}, ref-view{:0>2}, photo/geo/final-mask:{}/{}/{}".format(
+            scan_folder, ref_view, photo.mean(), geo.mean(), final.mean()))
+        vertexs.append(xyz.cpu().numpy())
+        vertex_colors.append(rgb.cpu().numpy())
+    xyz = np.concatenate(vertexs, axis=0) if vertexs else np.zeros((0, 3), np.float32)
+    rgb = np.concatenate(vertex_colors, axis=0) if vertex_colors else np.zeros((0, 3), np.uint8)
+    write_ply(plyfilename, xyz, rgb)
+    print("saving the final model to", plyfilename)
+    return xyz.shape[0]
+
+
+# ---------------------------------------------------------------------------------
 # file formats
 # ---------------------------------------------------------------------------------
 def read_img(filename):
@@ -261,3 +420,58 @@ def write_ply(filename, xyz, rgb=None):
     with open(filename, "wb") as f:
         f.write(header.encode("ascii"))
         f.write(v.tobytes())
+
+
+# ---------------------------------------------------------------------------------
+# command line (scripts/fusion_dtu.sh -> fusion.py, scripts/fusion_tnt.sh -> fusion_padding.py)
+# ---------------------------------------------------------------------------------
+DEFAULT_PHOTO_THRESHOLD = {"dtu": 0.35, "tnt": 0.3}   # fusion.py:285, fusion_padding.py:173
+
+
+def build_parser():
+    import argparse
+    p = argparse.ArgumentParser(prog="python -m aarmvs.fusion",
+                                description="Filter and fuse the depth maps of every scan of a list")
+    p.add_argument("--test_dataset", choices=["dtu", "tnt"], required=True,
+                   help="dtu: fusion.py's filter_depth; tnt: fusion_padding.py's")
+    p.add_argument("--testpath", required=True, help="folder of the scans (pair.txt, cams/, images/)")
+    p.add_argument("--testlist", required=True, help="text file, one scan name per line")
+    p.add_argument("--outdir", required=True, help="folder of the per-scan depth_est_0/ and confidence_0/")
+    p.add_argument("--photo_threshold", type=float, default=None,
+                   help="confidence threshold (default: 0.35 for dtu, 0.3 for tnt)")
+    p.add_argument("--device", default="cuda")
+    return p
+
+
+def parse_args(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.photo_threshold is None:
+        args.photo_threshold = DEFAULT_PHOTO_THRESHOLD[args.test_dataset]
+    return args
+
+
+def ply_path(outdir, scan, test_dataset):
+    """Where the scan's point cloud goes: outdir/<scan>.ply (fusion_padding.py:278,
+    fusion.py:289), but for DTU's scanN folders the name the DTU evaluation reads,
+    outdir/mvsnet_NNN_l3.ply (fusion.py:284-286)."""
+    if test_dataset == "dtu" and scan.startswith("scan") and scan[4:].isdigit():
+        return os.path.join(outdir, "mvsnet_{:0>3}_l3.ply".format(int(scan[4:])))
+    return os.path.join(outdir, scan + ".ply")
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    with open(args.testlist) as f:
+        scans = [line.rstrip() for line in f if line.strip()]
+    for scan in scans:
+        scan_folder = os.path.join(args.testpath, scan)
+        out_folder = os.path.join(args.outdir, scan)
+        ply = ply_path(args.outdir, scan, args.test_dataset)
+        if args.test_dataset == "tnt":
+            filter_depth_tnt(scan_folder, out_folder, ply, args.photo_threshold, args.device)
+        else:
+            filter_depth(scan_folder, out_folder, ply, args.photo_threshold, args.device)
+
+
+if __name__ == "__main__":
+    main()

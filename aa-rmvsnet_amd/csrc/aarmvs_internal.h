@@ -150,6 +150,11 @@ struct CostArgs {
 // NCHW <-> NHWC copy of a [B][C][HW] / [B][HW][C] fp32 tensor (API edges only)
 // depth-map fusion core (fusion.hip)
 hipError_t launch_fusion_filter(const aarmvs_fusion_args* a, hipStream_t s);
+// one cv2.pyrDown level of an interleaved float32 image, and the ordered world points of a
+// reference view's kept pixels (fusion.hip)
+hipError_t launch_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t s);
+size_t fusion_points_workspace_bytes(int H, int W);
+hipError_t launch_fusion_points(const aarmvs_fusion_points_args* a, hipStream_t s);
 // xmax (optional, to_nhwc only): atomic max of |in| as float bits
 hipError_t launch_layout(const float* in, float* out, int B, int C, int HW, bool to_nhwc,
                          hipStream_t s, unsigned* xmax = nullptr);
@@ -345,6 +350,7 @@ enum KernelId : int {
   K_WGRAD0, K_WGRAD1, K_WGRAD2, K_WGRAD3, K_WGRAD4,
   K_GNB_PARTIAL, K_DECONV_BWD, K_BWD_SMALL, K_CBW_CHAIN, K_CBW_FEAT, K_CBW_SMALL,
   K_DECONV_WGRAD, K_HEAD_WGRAD, K_DEFORM,
+  K_PYR_DOWN, K_FUSION_POINTS,
   K_COUNT
 };
 extern bool g_prof_on;

@@ -97,7 +97,8 @@ static const char* kKernelNames[K_COUNT] = {
     "dgrad0", "dgrad1", "dgrad2", "dgrad3", "dgrad4",
     "wgrad0", "wgrad1", "wgrad2", "wgrad3", "wgrad4",
     "gnb_partial", "deconv_bwd", "bwd_small", "cbw_chain", "cbw_feat", "cbw_small",
-    "deconv_wgrad", "head_wgrad", "deform_sample"};
+    "deconv_wgrad", "head_wgrad", "deform_sample",
+    "pyr_down", "fusion_points"};
 
 static hipEvent_t prof_event() {
   if (g_prof_used == g_prof_pool.size()) {
@@ -930,6 +931,36 @@ int aarmvs_fusion_filter(const aarmvs_fusion_args* a, hipStream_t stream) {
     if (!a->src_depth[v]) return fail(AARMVS_ERR_INVALID, "fusion_filter: null src_depth pointer");
   hipError_t e = launch_fusion_filter(a, stream);
   return e == hipSuccess ? AARMVS_OK : hip_fail(e, "fusion_filter");
+}
+
+int aarmvs_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t stream) {
+  if (!src || !dst) return fail(AARMVS_ERR_INVALID, "pyr_down: null pointer argument");
+  if (H < 4 || W < 4 || (C != 1 && C != 3))
+    return fail(AARMVS_ERR_INVALID, "pyr_down: need H, W >= 4 and C = 1 or 3");
+  if ((long long)H * W * C >= (1LL << 31))
+    return fail(AARMVS_ERR_INVALID, "pyr_down: H * W * C must be below 2^31");
+  hipError_t e = launch_pyr_down(src, H, W, C, dst, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "pyr_down");
+}
+
+size_t aarmvs_fusion_points_workspace_bytes(int H, int W) {
+  if (H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) return 0;
+  return fusion_points_workspace_bytes(H, W);
+}
+
+int aarmvs_fusion_points(const aarmvs_fusion_points_args* a, hipStream_t stream) {
+  if (!a) return fail(AARMVS_ERR_INVALID, "fusion_points: null args");
+  if (a->H < 1 || a->W < 1 || (long long)a->H * a->W >= (1LL << 31))
+    return fail(AARMVS_ERR_INVALID, "fusion_points: need H, W >= 1 and H * W < 2^31");
+  if (!a->mask || !a->depth || !a->cams || !a->count || !a->workspace)
+    return fail(AARMVS_ERR_INVALID, "fusion_points: null pointer argument");
+  if (a->capacity < 0) return fail(AARMVS_ERR_INVALID, "fusion_points: negative capacity");
+  if (a->capacity > 0 && !a->xyz)
+    return fail(AARMVS_ERR_INVALID, "fusion_points: null xyz with capacity > 0");
+  if ((a->color == nullptr) != (a->rgb == nullptr))
+    return fail(AARMVS_ERR_INVALID, "fusion_points: color and rgb must both be set or both be null");
+  hipError_t e = launch_fusion_points(a, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "fusion_points");
 }
 
 size_t aarmvs_group_norm_scratch_bytes(int B, int C, int HW) {

@@ -148,4 +148,220 @@ hipError_t launch_fusion_filter(const aarmvs_fusion_args* in, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------
+// cv2.pyrDown of the reference image (fusion_padding.py:166): OpenCV's scalar float path
+// (imgproc/src/pyramids.cpp), every intermediate rounded to float32.  A block owns a tile of
+// kPyrTY x kPyrTX output pixels: the horizontal pass of the 2 kPyrTY + 3 source rows it
+// needs goes to LDS, the vertical pass reads it from there.
+// Algorithmic bytes: 4 C (H W + H W / 4).
+// ---------------------------------------------------------------------------------
+constexpr int kPyrTX = 32, kPyrTY = 8, kPyrRows = 2 * kPyrTY + 3;
+
+// BORDER_REFLECT_101 for i in [-2, n + 1], n >= 4
+__device__ __forceinline__ int reflect101(int i, int n) {
+  if (i < 0) i = -i;
+  if (i >= n) i = 2 * n - 2 - i;
+  return i;
+}
+
+// s0*6 + (sm1 + sp1)*4 + sm2 + sp2, summed left to right
+__device__ __forceinline__ float pyr_taps(float sm2, float sm1, float s0, float sp1, float sp2) {
+  float v = __fadd_rn(__fmul_rn(s0, 6.0f), __fmul_rn(__fadd_rn(sm1, sp1), 4.0f));
+  v = __fadd_rn(v, sm2);
+  return __fadd_rn(v, sp2);
+}
+
+template <int C>
+__global__ void __launch_bounds__(256) pyr_down_kernel(const float* __restrict__ src, int H, int W,
+                                                       float* __restrict__ dst, int Ho, int Wo) {
+  constexpr int RW = kPyrTX * C;
+  __shared__ float r[kPyrRows][RW];
+  const int x0 = blockIdx.x * kPyrTX, y0 = blockIdx.y * kPyrTY;
+  for (int j = threadIdx.x; j < kPyrRows * RW; j += 256) {
+    const int rr = j / RW, xc = j - rr * RW;
+    const int xo = x0 + xc / C, c = xc % C;
+    const int sy = 2 * y0 - 2 + rr;
+    // rows past 2 Ho and columns past Wo feed no output of this image (and lie beyond what
+    // the border rule covers)
+    if (sy > 2 * Ho || xo >= Wo) continue;
+    const float* s = src + (size_t)reflect101(sy, H) * W * C + c;
+    const int sx = 2 * xo;
+    r[rr][xc] = pyr_taps(s[reflect101(sx - 2, W) * C], s[reflect101(sx - 1, W) * C], s[sx * C],
+                         s[reflect101(sx + 1, W) * C], s[reflect101(sx + 2, W) * C]);
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < kPyrTY * RW; j += 256) {
+    const int ty = j / RW, xc = j - ty * RW;
+    const int yo = y0 + ty, xo = x0 + xc / C;
+    if (yo >= Ho || xo >= Wo) continue;
+    const float v = pyr_taps(r[2 * ty][xc], r[2 * ty + 1][xc], r[2 * ty + 2][xc], r[2 * ty + 3][xc],
+                             r[2 * ty + 4][xc]);
+    dst[((size_t)yo * Wo + x0) * C + xc] = __fmul_rn(v, 1.0f / 256.0f);
+  }
+}
+
+hipError_t launch_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t s) {
+  const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
+  const dim3 grid((Wo + kPyrTX - 1) / kPyrTX, (Ho + kPyrTY - 1) / kPyrTY);
+  if (grid.y > 65535u) return hipErrorInvalidValue;
+  ProfScope ps(s, K_PYR_DOWN);
+  if (C == 3)
+    hipLaunchKernelGGL(pyr_down_kernel<3>, grid, dim3(256), 0, s, src, H, W, dst, Ho, Wo);
+  else
+    hipLaunchKernelGGL(pyr_down_kernel<1>, grid, dim3(256), 0, s, src, H, W, dst, Ho, Wo);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
+// World points of the kept pixels, in pixel order (fusion.py:235-246,
+// fusion_padding.py:239-251).  A block owns kPtsChunk consecutive pixels, taken in
+// kPtsRounds rounds of one pixel per thread.  Three launches: the kept pixels of every block,
+// an exclusive scan of those counts by one workgroup (tile after tile, with a carry), and the
+// write pass, where a pixel's rank is its block's offset + the kept pixels of the block's
+// earlier (round, wave) groups + the set ballot bits below its lane.
+// Algorithmic bytes: 1 per pixel + (8 depth + 12 colour + 12 xyz + 3 rgb) per kept pixel.
+// ---------------------------------------------------------------------------------
+constexpr int kPtsThreads = 256, kPtsRounds = 4, kPtsWaves = kPtsThreads / 64;
+constexpr int kPtsChunk = kPtsThreads * kPtsRounds;
+constexpr int kScanThreads = 256;   // block counts per scan tile
+
+struct PointsArgs {
+  int HW, W;
+  const unsigned char* mask;
+  const double* depth;
+  const float* color;
+  float invK[9], invE[16];
+  float* xyz;
+  unsigned char* rgb;
+  long long capacity;
+  const int* block_off;
+};
+
+__global__ void __launch_bounds__(kPtsThreads) points_count_kernel(const unsigned char* __restrict__ mask,
+                                                                   int HW, int* __restrict__ block_cnt) {
+  __shared__ int wcnt[kPtsWaves];
+  const long long base = (long long)blockIdx.x * kPtsChunk;
+  int c = 0;
+#pragma unroll
+  for (int r = 0; r < kPtsRounds; ++r) {
+    const long long p = base + r * kPtsThreads + threadIdx.x;
+    const bool keep = p < HW && mask[p] != 0;
+    c += __popcll(__ballot(keep));
+  }
+  if ((threadIdx.x & 63) == 0) wcnt[threadIdx.x >> 6] = c;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int t = 0;
+#pragma unroll
+    for (int w = 0; w < kPtsWaves; ++w) t += wcnt[w];
+    block_cnt[blockIdx.x] = t;
+  }
+}
+
+// cnt[0 .. n) -> its exclusive prefix sums, in place; *total = the sum (< 2^31: H W is)
+__global__ void __launch_bounds__(kScanThreads) points_scan_kernel(int* __restrict__ cnt, int n,
+                                                                   long long* __restrict__ total) {
+  __shared__ int wsum[kScanThreads / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int carry = 0;
+  for (int base = 0; base < n; base += kScanThreads) {
+    const int i = base + threadIdx.x;
+    const int v = i < n ? cnt[i] : 0;
+    int s = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int t = __shfl_up(s, d);
+      if (lane >= d) s += t;
+    }
+    if (lane == 63) wsum[wave] = s;
+    __syncthreads();
+    int before = 0, tile = 0;
+#pragma unroll
+    for (int w = 0; w < kScanThreads / 64; ++w) {
+      before += w < wave ? wsum[w] : 0;
+      tile += wsum[w];
+    }
+    if (i < n) cnt[i] = carry + before + s - v;
+    carry += tile;
+    __syncthreads();   // wsum is rewritten by the next tile
+  }
+  if (threadIdx.x == 0) *total = carry;
+}
+
+__global__ void __launch_bounds__(kPtsThreads) points_write_kernel(PointsArgs a) {
+  __shared__ int wcnt[kPtsRounds][kPtsWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long base = (long long)blockIdx.x * kPtsChunk;
+  bool keep[kPtsRounds];
+  int below[kPtsRounds];
+#pragma unroll
+  for (int r = 0; r < kPtsRounds; ++r) {
+    const long long p = base + r * kPtsThreads + threadIdx.x;
+    keep[r] = p < a.HW && a.mask[p] != 0;
+    const unsigned long long b = __ballot(keep[r]);
+    below[r] = __popcll(b & ((1ULL << lane) - 1ULL));
+    if (lane == 0) wcnt[r][wave] = __popcll(b);
+  }
+  __syncthreads();
+  long long acc = a.block_off[blockIdx.x];
+#pragma unroll
+  for (int r = 0; r < kPtsRounds; ++r) {
+    int before = 0, round = 0;
+#pragma unroll
+    for (int w = 0; w < kPtsWaves; ++w) {
+      before += w < wave ? wcnt[r][w] : 0;
+      round += wcnt[r][w];
+    }
+    const long long rank = acc + before + below[r];
+    acc += round;
+    if (!keep[r] || rank >= a.capacity) continue;
+    const int p = (int)(base + r * kPtsThreads + threadIdx.x);
+    const int y = p / a.W, x = p - y * a.W;
+    const double d = a.depth[p];
+    const double b[3] = {(double)x * d, (double)y * d, d};
+    const double xr[4] = {mrow<3>(a.invK, 0, b), mrow<3>(a.invK, 1, b), mrow<3>(a.invK, 2, b), 1.0};
+    float* o = a.xyz + (size_t)rank * 3;
+    o[0] = (float)mrow<4>(a.invE, 0, xr);
+    o[1] = (float)mrow<4>(a.invE, 1, xr);
+    o[2] = (float)mrow<4>(a.invE, 2, xr);
+    if (a.color) {
+      const float* c = a.color + (size_t)p * 3;
+      unsigned char* q = a.rgb + (size_t)rank * 3;
+      q[0] = (unsigned char)(int)__fmul_rn(c[0], 255.0f);
+      q[1] = (unsigned char)(int)__fmul_rn(c[1], 255.0f);
+      q[2] = (unsigned char)(int)__fmul_rn(c[2], 255.0f);
+    }
+  }
+}
+
+static int points_blocks(int H, int W) {
+  return (int)(((long long)H * W + kPtsChunk - 1) / kPtsChunk);
+}
+
+size_t fusion_points_workspace_bytes(int H, int W) {
+  return ((size_t)points_blocks(H, W) * sizeof(int) + 255) / 256 * 256;
+}
+
+hipError_t launch_fusion_points(const aarmvs_fusion_points_args* in, hipStream_t s) {
+  PointsArgs a{};
+  a.HW = in->H * in->W;
+  a.W = in->W;
+  a.mask = in->mask;
+  a.depth = in->depth;
+  a.color = in->color;
+  for (int i = 0; i < 9; ++i) a.invK[i] = in->cams[i];
+  for (int i = 0; i < 16; ++i) a.invE[i] = in->cams[9 + i];
+  a.xyz = in->xyz;
+  a.rgb = in->rgb;
+  a.capacity = in->capacity;
+  int* blk = static_cast<int*>(in->workspace);
+  a.block_off = blk;
+  const int nb = points_blocks(in->H, in->W);
+  ProfScope ps(s, K_FUSION_POINTS);
+  hipLaunchKernelGGL(points_count_kernel, dim3(nb), dim3(kPtsThreads), 0, s, a.mask, a.HW, blk);
+  hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, blk, nb, in->count);
+  hipLaunchKernelGGL(points_write_kernel, dim3(nb), dim3(kPtsThreads), 0, s, a);
+  return hipGetLastError();
+}
+
 }  // namespace aarmvs

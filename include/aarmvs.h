@@ -301,6 +301,44 @@ typedef struct aarmvs_fusion_args {
 int aarmvs_fusion_filter(const aarmvs_fusion_args* args, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * One level of OpenCV's 5x5 Gaussian pyramid (cv2.pyrDown, imgproc/src/pyramids.cpp, the
+ * scalar float path), which fusion_padding.py:166 applies to the reference image: `src`
+ * device float32 [H,W,C] interleaved, C = 1 or 3; `dst` device [(H+1)/2, (W+1)/2, C].
+ * Horizontal pass per source row, r[x] = s[2x]*6 + (s[2x-1] + s[2x+1])*4 + s[2x-2] +
+ * s[2x+2], then the same expression down the rows 2y-2 .. 2y+2 of r and * (1/256); the sums
+ * run left to right, every intermediate is rounded to float32 (no fused multiply-add), and
+ * out-of-range indices follow BORDER_REFLECT_101.  H, W >= 4.
+ * ------------------------------------------------------------------------- */
+int aarmvs_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * World points of one reference view's kept pixels (fusion.py:235-246,
+ * fusion_padding.py:239-251): for every pixel with a nonzero `mask`, in row-major pixel
+ * order (numpy's x[valid_points]), xyz = (inv(E) {inv(K) {x d, y d, d}, 1})[:3] in float64 on
+ * the float32 matrices (numpy's matmul rounding, as aarmvs_fusion_filter), cast to float32,
+ * and rgb = (unsigned char)(color * 255) in float32 (truncating).  The position of a point
+ * in the output is its rank among the kept pixels (block counts, an exclusive scan, in-block
+ * ranks: no atomics), so the result is the same on every run.  Points of rank >= capacity
+ * are not written; `count` always receives the total number of kept pixels.  Stream-ordered:
+ * nothing here waits for the device.  H * W < 2^31.
+ * ------------------------------------------------------------------------- */
+typedef struct aarmvs_fusion_points_args {
+  int H, W;
+  const unsigned char* mask;   /* [H,W] device, nonzero = keep                          */
+  const double* depth;         /* [H,W] device, the averaged depth                      */
+  const float* color;          /* [H,W,3] device in [0,1], or NULL                      */
+  const float* cams;           /* HOST: inv(K_ref) 3x3 then inv(E_ref) 4x4, float32
+                                  row-major, as numpy forms them                        */
+  float* xyz;                  /* [capacity,3] device out                               */
+  unsigned char* rgb;          /* [capacity,3] device out; NULL if and only if color is */
+  long long capacity;          /* points that xyz / rgb have room for (>= 0)            */
+  long long* count;            /* device out: number of kept pixels                     */
+  void* workspace;             /* device, aarmvs_fusion_points_workspace_bytes(H, W)    */
+} aarmvs_fusion_points_args;
+size_t aarmvs_fusion_points_workspace_bytes(int H, int W);
+int aarmvs_fusion_points(const aarmvs_fusion_points_args* args, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Epilogue of the evidential head (evidential/models.py:385-459): from the three
  * classifier outputs head[i] = classif_i(...) [1][4][D][H][W] (channels: cost, log nu, log
  * alpha, log beta; at the head's full [maxdisp, H, W] resolution, where get_pred / get_logits'
