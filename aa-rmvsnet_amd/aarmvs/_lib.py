@@ -153,6 +153,11 @@ SIGNATURES = {
     "aarmvs_deform_sample": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8 + [c_void_p, c_void_p]),
     "aarmvs_deform_sample_backward": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 8
                                       + [c_void_p] * 5),
+    "aarmvs_cls_loss_scratch_bytes": (c_size_t, [c_int, c_int]),
+    "aarmvs_cls_loss": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p] * 8),
+    "aarmvs_cls_loss_backward": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p, c_void_p]),
+    "aarmvs_depth_metrics": (c_int, [c_void_p] * 3 + [c_int, c_int, ctypes.POINTER(ctypes.c_float),
+                                                      c_int, c_void_p, c_void_p, c_void_p]),
     "aarmvs_profile_enable": (None, [c_int]),
     "aarmvs_profile_reset": (None, []),
     "aarmvs_profile_kernel_count": (c_int, []),

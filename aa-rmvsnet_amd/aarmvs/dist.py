@@ -51,6 +51,18 @@ def max_over_ranks(value: float, device=None) -> float:
     return float(t.item())
 
 
+def sum_over_ranks(values, device=None) -> list:
+    """Element-wise sum of a list of host floats over all ranks, in float64 (identity without a
+    process group)."""
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+        return [float(v) for v in values]
+    if dist.get_backend() == "gloo":
+        device = None
+    t = torch.tensor(list(values), dtype=torch.float64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    return t.tolist()
+
+
 def init_process_group(device: torch.device | None = None) -> None:
     """nccl (= RCCL on ROCm) on GPUs, gloo on CPU; no-op for a single process."""
     _, _, world = env()

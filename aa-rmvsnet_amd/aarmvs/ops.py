@@ -241,6 +241,108 @@ def softmax_depth(cost: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _cls_scratch(B: int, HW: int, device) -> torch.Tensor:
+    n = lib().aarmvs_cls_loss_scratch_bytes(B, HW)
+    if n == 0:
+        raise AarmvsError(f"aarmvs: cls_loss geometry B={B} HW={HW}: "
+                          + lib().aarmvs_last_error().decode(errors="replace"))
+    return torch.empty(n // 8, dtype=torch.float64, device=device)
+
+
+@_on_tensor_device
+def cls_loss_forward(cost: torch.Tensor, depth_gt: torch.Tensor, mask: torch.Tensor,
+                     depth_values: torch.Tensor, want_prob_map: bool = False) -> dict:
+    """aarmvs_cls_loss on cost [B,D,H,W], depth_gt / mask [B,H,W], depth_values [B,D]: every
+    output of the kernel, {'cost' (contiguous), 'mask', 'loss' (0-dim), 'wta_depth' [B,H,W],
+    'max_prob' [B,H,W] or None, 'lse' [2,B,H,W], 'gt' [B,H,W] int32, 'coef' [B]}.  No autograd:
+    ``cls_loss`` is the differentiable form."""
+    _require_device(cost, depth_gt, mask, depth_values)
+    c, gtd, mk, dv = (t.detach().contiguous() for t in (cost, depth_gt, mask, depth_values))
+    if c.dim() != 4:
+        raise AarmvsError(f"aarmvs: cls_loss cost must be [B,D,H,W], got {tuple(c.shape)}")
+    B, D, H, W = c.shape
+    if tuple(gtd.shape) != (B, H, W) or tuple(mk.shape) != (B, H, W) or tuple(dv.shape) != (B, D):
+        raise AarmvsError(f"aarmvs: cls_loss shapes: cost {tuple(c.shape)}, depth_gt "
+                          f"{tuple(gtd.shape)}, mask {tuple(mk.shape)}, depth_values {tuple(dv.shape)}")
+    dev = c.device
+    if any(t.device != dev for t in (gtd, mk, dv)):
+        raise AarmvsError("aarmvs: cls_loss tensors must be on one device")
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"cost": c, "mask": mk, "loss": torch.empty((), **f32), "wta_depth": torch.empty(B, H, W, **f32),
+           "max_prob": torch.empty(B, H, W, **f32) if want_prob_map else None,
+           "lse": torch.empty(2, B, H, W, **f32),
+           "gt": torch.empty(B, H, W, dtype=torch.int32, device=dev), "coef": torch.empty(B, **f32)}
+    scratch = _cls_scratch(B, H * W, dev)
+    check(lib().aarmvs_cls_loss(c.data_ptr(), gtd.data_ptr(), mk.data_ptr(), dv.data_ptr(), B, D, H * W,
+                                out["loss"].data_ptr(), out["wta_depth"].data_ptr(),
+                                _ptr(out["max_prob"]), out["lse"].data_ptr(), out["gt"].data_ptr(),
+                                out["coef"].data_ptr(), scratch.data_ptr(), _stream()), "cls_loss")
+    return out
+
+
+class _ClsLoss(torch.autograd.Function):
+    """loss (and the non-differentiable WTA depth / max probability) from the cost volume on
+    aarmvs_cls_loss; the backward is aarmvs_cls_loss_backward (p - onehot, scaled), which reads
+    the upstream gradient on the device.  Saves cost, lse, gt, mask and coef only."""
+
+    @staticmethod
+    def forward(ctx, cost, depth_gt, mask, depth_values, want_prob_map):
+        o = cls_loss_forward(cost, depth_gt, mask, depth_values, want_prob_map)
+        ctx.save_for_backward(o["cost"], o["lse"], o["gt"], o["mask"], o["coef"])
+        outs = (o["loss"], o["wta_depth"]) + ((o["max_prob"],) if want_prob_map else ())
+        ctx.mark_non_differentiable(*outs[1:])
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, *_):
+        cost, lse, gt, mask, coef = ctx.saved_tensors
+        B, D, H, W = cost.shape
+        g = g_loss.detach().to(cost.device, torch.float32).reshape(1).contiguous()
+        grad = torch.empty_like(cost)
+        with torch.cuda.device(cost.device):
+            check(lib().aarmvs_cls_loss_backward(cost.data_ptr(), lse.data_ptr(), gt.data_ptr(),
+                                                 mask.data_ptr(), coef.data_ptr(), g.data_ptr(), B, D,
+                                                 H * W, grad.data_ptr(), _stream()), "cls_loss_backward")
+        return grad, None, None, None, None
+
+
+def cls_loss(cost: torch.Tensor, depth_gt: torch.Tensor, mask: torch.Tensor, depth_values: torch.Tensor,
+             want_prob_map: bool = False):
+    """mvsnet_cls_loss(softmax(cost, 1), depth_gt, mask, depth_values) without the probability
+    volume: (loss, wta_depth[, max_prob]); ``loss`` is differentiable w.r.t. ``cost``."""
+    _require_device(cost, depth_gt, mask, depth_values)
+    return _ClsLoss.apply(cost, depth_gt, mask, depth_values, bool(want_prob_map))
+
+
+@_on_tensor_device
+def depth_metrics(depth_est: torch.Tensor, depth_gt: torch.Tensor, mask: torch.Tensor,
+                  thresholds=(2, 4, 8, 16, 32)) -> dict:
+    """The test pass's masked metrics (utils.py:150-175 over mask > 0.5, the mean over batch
+    elements of each element's masked mean) under the reference's key names: abs_depth_error and
+    thres{t}mm_error per threshold, as 0-dim float64 device tensors (no host synchronisation)."""
+    _require_device(depth_est, depth_gt, mask)
+    est, gtd, mk = (t.detach().contiguous() for t in (depth_est, depth_gt, mask))
+    if est.dim() != 3 or gtd.shape != est.shape or mk.shape != est.shape:
+        raise AarmvsError(f"aarmvs: depth_metrics needs three [B,H,W] tensors, got {tuple(est.shape)}, "
+                          f"{tuple(gtd.shape)}, {tuple(mk.shape)}")
+    if gtd.device != est.device or mk.device != est.device:
+        raise AarmvsError("aarmvs: depth_metrics tensors must be on one device")
+    thr = list(thresholds)
+    if len(thr) > 8:
+        raise AarmvsError(f"aarmvs: depth_metrics takes at most 8 thresholds, got {len(thr)}")
+    B, H, W = est.shape
+    out = torch.empty(1 + len(thr), dtype=torch.float64, device=est.device)
+    scratch = _cls_scratch(B, H * W, est.device)
+    check(lib().aarmvs_depth_metrics(est.data_ptr(), gtd.data_ptr(), mk.data_ptr(), B, H * W,
+                                     (ctypes.c_float * max(1, len(thr)))(*thr), len(thr),
+                                     out.data_ptr(), scratch.data_ptr(), _stream()), "depth_metrics")
+    res = {"abs_depth_error": out[0]}
+    for k, t in enumerate(thr):
+        res[f"thres{t:g}mm_error"] = out[1 + k]
+    return res
+
+
 def _ptr3(ts) -> ctypes.Array:
     return (ctypes.c_void_p * 3)(*[t.data_ptr() for t in ts])
 

@@ -11,8 +11,17 @@ wrapped model's keys, ``module.``-prefixed under DDP as under train.py's DataPar
 ``--resume`` from the latest of them.
 
 Loss: ``loss_der`` on the evidential outputs where the head runs (B = 1, D = 32: train.py:297-
-304), otherwise the core ``mvsnet_cls_loss`` (the head cannot train at D = 192).
-tensorboard summaries and the per-epoch test pass of train.py are not reproduced.
+304), otherwise the core ``mvsnet_cls_loss`` (SURVEY §8e: the head cannot train at D = 192);
+with ``--fused_loss`` the model hands over the raw cost volume and the loss is
+``mvsnet_cls_loss_from_cost`` (HIP: no probability volume).
+
+``--testpath/--testlist`` add train.py's per-epoch test pass (train.py:259-285, test_sample):
+eval mode, no grad, the same loss as training and the six masked depth metrics
+(``aarmvs.ops.depth_metrics``) of the loss's depth map, averaged over batches as
+DictAverageMeter does.  Each rank takes its contiguous shard of the test samples
+(``aarmvs.dist.shard_range``); the per-batch sums and batch counts are all-reduced, rank 0
+prints ``avg_test_scalars:``.  The evidential scalars, tensorboard summaries and the image /
+.pt dumps of test_sample are not reproduced.
 
 usage: python -m torch.distributed.run --nproc-per-node 8 -m aarmvs.train_ddp \\
            --trainpath DTU --trainlist lists/train.txt --numdepth 192 --logdir ckpt
@@ -30,7 +39,7 @@ import torch
 from torch.utils.data import DataLoader
 from torch.utils.data.distributed import DistributedSampler
 
-from .dist import env, init_process_group, local_device_index
+from .dist import env, init_process_group, local_device_index, shard_range, sum_over_ranks
 
 
 def parse_args(argv=None):
@@ -59,6 +68,13 @@ def parse_args(argv=None):
     ap.add_argument("--max_steps", type=int, default=0, help="stop each epoch after this many steps (0: all)")
     ap.add_argument("--train_light_idx", type=int, default=-1,
                     help="light index of the training images (train.py: -1, all seven)")
+    ap.add_argument("--fused_loss", action="store_true",
+                    help="loss from the raw cost volume on the HIP kernels (where the evidential "
+                         "head does not run)")
+    ap.add_argument("--testpath", default=None, help="test datapath: run train.py's per-epoch test pass")
+    ap.add_argument("--testlist", default=None, help="test list")
+    ap.add_argument("--test_light_idx", type=int, default=3,
+                    help="light index of the test images (train.py --light_idx: 3)")
     return ap.parse_args(argv)
 
 
@@ -66,11 +82,49 @@ def _strip_module(state):
     return OrderedDict((k[7:] if k.startswith("module.") else k, v) for k, v in state.items())
 
 
-def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
-    """Runs train.py's epochs on this rank's shard; returns {'losses', 'checkpoints'}."""
-    from datasets import find_dataset_def
+TEST_THRESHOLDS = (2, 4, 8, 16, 32)
+
+
+def _loss_and_depth(out, s, fused: bool):
+    """The training loss of one batch and the depth map it comes with (train.py:297-304)."""
     from evidential.models import loss_der
-    from models import EMVSNet, mvsnet_cls_loss
+    from models import mvsnet_cls_loss, mvsnet_cls_loss_from_cost
+    first, evidential, _ = out
+    if evidential is not None:   # loss_der reads the evidential prediction only
+        return loss_der({"probability_volume": first, "evidential_prediction": evidential},
+                        s["depth"], s["mask"], s["depth_values"])[:2]
+    if fused:
+        return mvsnet_cls_loss_from_cost(first, s["depth"], s["mask"], s["depth_values"])
+    return mvsnet_cls_loss(first, s["depth"], s["mask"], s["depth_values"])
+
+
+def run_test_pass(model, loader, device, fused: bool, rank: int = 0, log=print) -> dict:
+    """train.py:259-285 on this rank's loader: per batch the loss and the masked metrics of its
+    depth map, summed over batches and ranks, divided by the batch count."""
+    from . import ops
+    keys = ["loss", "abs_depth_error"] + [f"thres{t}mm_error" for t in TEST_THRESHOLDS]
+    sums, count = [0.0] * len(keys), 0
+    model.eval()
+    with torch.no_grad():
+        for sample in loader:
+            s = {k: v.to(device) if torch.is_tensor(v) else v for k, v in sample.items()}
+            loss, depth_est = _loss_and_depth(model(s["imgs"], s["proj_matrices"], s["depth_values"]),
+                                              s, fused)
+            m = ops.depth_metrics(depth_est.float(), s["depth"].float(), s["mask"].float(),
+                                  TEST_THRESHOLDS)
+            row = torch.stack([loss.double().reshape(())] + [m[k] for k in keys[1:]]).tolist()
+            sums = [a + b for a, b in zip(sums, row)]
+            count += 1
+    total = sum_over_ranks(sums + [float(count)], device)
+    log(f"test pass: rank {rank} ran {count} of {int(total[-1])} test batches")
+    return {k: v / total[-1] for k, v in zip(keys, total)} if total[-1] else {}
+
+
+def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
+    """Runs train.py's epochs on this rank's shard; returns {'losses', 'checkpoints',
+    'test_scalars' (one dict per epoch when --testpath is given, else empty)}."""
+    from datasets import find_dataset_def
+    from models import EMVSNet
     device = torch.device(device or f"cuda:{local_device_index(env()[1])}")
     if device.type == "cuda":
         if device.index is None:
@@ -85,8 +139,15 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
     sampler = DistributedSampler(ds, num_replicas=world, rank=rank, shuffle=True, seed=args.seed,
                                  drop_last=True)
     loader = DataLoader(ds, args.batch_size, sampler=sampler, num_workers=0, drop_last=True)
+    test_loader = None
+    if args.testpath:
+        tds = find_dataset_def(args.dataset)(args.testpath, args.testlist, "test", args.view_num,
+                                             args.numdepth, args.interval_scale, args.inverse_depth,
+                                             args.origin_size, args.test_light_idx, args.image_scale)
+        shard = torch.utils.data.Subset(tds, list(shard_range(len(tds), rank, world)))
+        test_loader = DataLoader(shard, args.batch_size, shuffle=False, num_workers=0, drop_last=False)
     model = EMVSNet(disparity_level=args.numdepth, image_scale=args.image_scale,
-                    max_h=args.max_h, max_w=args.max_w)
+                    max_h=args.max_h, max_w=args.max_w, return_cost=args.fused_loss)
     if args.loadckpt:   # train.py:150-170: tensors only, any 'module.' prefix removed
         state = torch.load(args.loadckpt, map_location="cpu", weights_only=True)["model"]
         model.load_state_dict(_strip_module(state), strict=True)
@@ -113,7 +174,7 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
         sched.step()
     if rank == 0:
         os.makedirs(args.logdir, exist_ok=True)
-    losses, ckpts = [], []
+    losses, ckpts, test_scalars = [], [], []
     for epoch in range(start_epoch, args.epochs):
         sampler.set_epoch(epoch)
         for step, sample in enumerate(loader):
@@ -123,12 +184,8 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
             model.train()
             optimizer.zero_grad()
             s = {k: v.to(device) if torch.is_tensor(v) else v for k, v in sample.items()}
-            prob, evidential, _ = model(s["imgs"], s["proj_matrices"], s["depth_values"])
-            if evidential is not None:   # train.py:297-304
-                loss = loss_der({"probability_volume": prob, "evidential_prediction": evidential},
-                                s["depth"], s["mask"], s["depth_values"])[0]
-            else:
-                loss = mvsnet_cls_loss(prob, s["depth"], s["mask"], s["depth_values"])[0]
+            loss = _loss_and_depth(model(s["imgs"], s["proj_matrices"], s["depth_values"]), s,
+                                   args.fused_loss)[0]
             loss.backward()
             optimizer.step()
             losses.append(float(loss))
@@ -142,7 +199,14 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
             torch.save({"epoch": epoch, "model": model.state_dict(),
                         "optimizer": optimizer.state_dict()}, path)
             ckpts.append(path)
-    return {"losses": losses, "checkpoints": ckpts}
+        if test_loader is not None:   # train.py:259-285
+            # the bare module: ranks may hold different numbers of test batches, and DDP's
+            # forward synchronises buffers across ranks
+            core = model.module if isinstance(model, torch.nn.parallel.DistributedDataParallel) else model
+            test_scalars.append(run_test_pass(core, test_loader, device, args.fused_loss, rank, log))
+            if rank == 0:
+                log("avg_test_scalars:", test_scalars[-1])
+    return {"losses": losses, "checkpoints": ckpts, "test_scalars": test_scalars}
 
 
 def main(argv=None) -> int:

@@ -251,6 +251,22 @@ hipError_t launch_lstm_gates_bwd(const float* z, const float* c_prev, const floa
 hipError_t launch_group_norm_bwd(const float* dy, const float* x, const float* gamma,
                                  const float* mean_rstd, int B, int C, int HW, int G, float* dx,
                                  float* s1, float* s2, void* scratch, hipStream_t s);
+// The classification loss from the cost volume and the masked depth metrics (cls_loss.hip).
+// Their scratch holds [B][cls_loss_blocks(HW)][kClsPartials] fp64 per-block partials (the loss
+// uses two of the slots, the metrics 2 + the thresholds); lse is [2][B][HW] (an fp32 pair).
+constexpr int kClsPartials = 2 + AARMVS_MAX_THRESHOLDS;
+int cls_loss_blocks(int HW);
+hipError_t launch_cls_loss_fwd(const float* cost, const float* depth_gt, const float* mask,
+                               const float* dvals, int B, int D, int HW, float* loss,
+                               float* wta_depth, float* max_prob, float* lse, int* gt, float* coef,
+                               void* scratch, hipStream_t s);
+hipError_t launch_cls_loss_bwd(const float* cost, const float* lse, const int* gt, const float* mask,
+                               const float* coef, const float* g, int B, int D, int HW,
+                               float* grad_cost, hipStream_t s);
+// thresholds: a host array of nthr values
+hipError_t launch_depth_metrics(const float* est, const float* gt, const float* mask, int B, int HW,
+                                const float* thresholds, int nthr, double* out, void* scratch,
+                                hipStream_t s);
 
 int cu_count();
 
@@ -351,6 +367,7 @@ enum KernelId : int {
   K_GNB_PARTIAL, K_DECONV_BWD, K_BWD_SMALL, K_CBW_CHAIN, K_CBW_FEAT, K_CBW_SMALL,
   K_DECONV_WGRAD, K_HEAD_WGRAD, K_DEFORM,
   K_PYR_DOWN, K_FUSION_POINTS,
+  K_CLS_LOSS_FWD, K_CLS_LOSS_REDUCE, K_CLS_LOSS_BWD, K_DEPTH_METRICS,
   K_COUNT
 };
 extern bool g_prof_on;

@@ -98,7 +98,8 @@ static const char* kKernelNames[K_COUNT] = {
     "wgrad0", "wgrad1", "wgrad2", "wgrad3", "wgrad4",
     "gnb_partial", "deconv_bwd", "bwd_small", "cbw_chain", "cbw_feat", "cbw_small",
     "deconv_wgrad", "head_wgrad", "deform_sample",
-    "pyr_down", "fusion_points"};
+    "pyr_down", "fusion_points",
+    "cls_loss_fwd", "cls_loss_reduce", "cls_loss_bwd", "depth_metrics"};
 
 static hipEvent_t prof_event() {
   if (g_prof_used == g_prof_pool.size()) {
@@ -1088,6 +1089,58 @@ int aarmvs_deform_sample_backward(const float* x_nhwc, const float* offset, cons
   a.gm = mask ? grad_mask : nullptr;
   hipError_t e = launch_deform_sample(a, true, stream);
   return e == hipSuccess ? AARMVS_OK : hip_fail(e, "deform_sample_backward");
+}
+
+// B rides in gridDim.y; the pixel index of a block's last thread must fit an int
+static int cls_check(const char* who, int B, int HW) {
+  if (B < 1 || HW < 1) return fail(AARMVS_ERR_INVALID, std::string(who) + ": need B, HW >= 1");
+  if (B > 65535 || HW > 0x7fffffff - 256)
+    return fail(AARMVS_ERR_INVALID, std::string(who) + ": need B <= 65535 and HW < 2^31 - 256");
+  return AARMVS_OK;
+}
+
+size_t aarmvs_cls_loss_scratch_bytes(int B, int HW) {
+  if (cls_check("cls_loss_scratch_bytes", B, HW)) return 0;
+  return (size_t)B * cls_loss_blocks(HW) * kClsPartials * sizeof(double);
+}
+
+int aarmvs_cls_loss(const float* cost, const float* depth_gt, const float* mask,
+                    const float* depth_values, int B, int D, int HW, float* loss, float* wta_depth,
+                    float* max_prob, float* lse, int* gt_index, float* coef, void* scratch,
+                    hipStream_t stream) {
+  if (!cost || !depth_gt || !mask || !depth_values || !loss || !wta_depth || !lse || !gt_index ||
+      !coef || !scratch)
+    return fail(AARMVS_ERR_INVALID, "cls_loss: null pointer argument");
+  if (int rc = cls_check("cls_loss", B, HW)) return rc;
+  if (D < 1) return fail(AARMVS_ERR_INVALID, "cls_loss: need D >= 1");
+  hipError_t e = launch_cls_loss_fwd(cost, depth_gt, mask, depth_values, B, D, HW, loss, wta_depth,
+                                     max_prob, lse, gt_index, coef, scratch, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "cls_loss");
+}
+
+int aarmvs_cls_loss_backward(const float* cost, const float* lse, const int* gt_index,
+                             const float* mask, const float* coef, const float* grad_loss, int B,
+                             int D, int HW, float* grad_cost, hipStream_t stream) {
+  if (!cost || !lse || !gt_index || !mask || !coef || !grad_loss || !grad_cost)
+    return fail(AARMVS_ERR_INVALID, "cls_loss_backward: null pointer argument");
+  if (int rc = cls_check("cls_loss_backward", B, HW)) return rc;
+  if (D < 1) return fail(AARMVS_ERR_INVALID, "cls_loss_backward: need D >= 1");
+  hipError_t e = launch_cls_loss_bwd(cost, lse, gt_index, mask, coef, grad_loss, B, D, HW, grad_cost,
+                                     stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "cls_loss_backward");
+}
+
+int aarmvs_depth_metrics(const float* depth_est, const float* depth_gt, const float* mask, int B,
+                         int HW, const float* thresholds, int n_thresholds, double* out,
+                         void* scratch, hipStream_t stream) {
+  if (!depth_est || !depth_gt || !mask || !out || !scratch || (n_thresholds > 0 && !thresholds))
+    return fail(AARMVS_ERR_INVALID, "depth_metrics: null pointer argument");
+  if (int rc = cls_check("depth_metrics", B, HW)) return rc;
+  if (n_thresholds < 0 || n_thresholds > AARMVS_MAX_THRESHOLDS)
+    return fail(AARMVS_ERR_INVALID, "depth_metrics: at most 8 thresholds");
+  hipError_t e = launch_depth_metrics(depth_est, depth_gt, mask, B, HW, thresholds, n_thresholds, out,
+                                      scratch, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "depth_metrics");
 }
 
 }  // extern "C"

@@ -47,8 +47,8 @@ from .module import (ConvLSTMCell, convgnrelu, deConvGnReLU, deformconvgnrelu,
 
 __all__ = [
     "IntraViewAAModule", "InterViewAAModule", "FeatNet", "UNetConvLSTM", "EMVSNet",
-    "mvsnet_cls_loss", "EvidentialUnavailable", "EvidentialModule", "EvidentialShapeError",
-    "loss_der", "loss_emvsnet", "criterion_uncertainty",
+    "mvsnet_cls_loss", "mvsnet_cls_loss_from_cost", "EvidentialUnavailable", "EvidentialModule",
+    "EvidentialShapeError", "loss_der", "loss_emvsnet", "criterion_uncertainty",
     "homo_warping_depthwise", "ConvLSTMCell", "convgnrelu", "DeformConv2d", "deformconvgnrelu",
     "ResnetBlockGn", "resnet_block_gn", "deConvGnReLU",
 ]
@@ -264,7 +264,7 @@ class EMVSNet(nn.Module):
                      "warp gather/scatter) on gfx950")
 
     def __init__(self, disparity_level, image_scale=0.25, max_h=960, max_w=480, return_depth=False,
-                 evidential=True):
+                 evidential=True, return_cost=False):
         super().__init__()
         self.feature = FeatNet()
         input_size = (int(max_h * image_scale), int(max_w * image_scale))
@@ -280,6 +280,9 @@ class EMVSNet(nn.Module):
             self.evidential = EvidentialUnavailable(depth=disparity_level)
         self.evidential_strict = evidential == "strict"
         self.return_depth = return_depth
+        # train forward only: the raw cost volume in the first slot instead of its softmax, for
+        # mvsnet_cls_loss_from_cost (no probability volume is formed unless the head runs)
+        self.return_cost = return_cost
         self._sweep_cache = None
 
     # -- HIP sweep object, repacked whenever a sweep parameter changed ---------------
@@ -326,6 +329,11 @@ class EMVSNet(nn.Module):
             else:
                 cost = sweep(ref, srcs, ref_proj, src_projs, dv, want_depth=False,
                              want_cost=True)["cost"]
+            if self.return_cost:
+                evidential, prob_combine = None, None
+                if evidential_on:
+                    evidential, prob_combine = self.evidential(_SoftmaxDepth.apply(cost), depth_values)
+                return cost, evidential, prob_combine
             prob = _SoftmaxDepth.apply(cost)
             evidential, prob_combine = None, None
             if evidential_on:
@@ -359,3 +367,14 @@ def mvsnet_cls_loss(prob_volume, depth_gt, mask, depth_value, return_prob_map=Fa
     if return_prob_map:
         return loss, wta, prob_volume.max(dim=1)[0]
     return loss, wta
+
+
+def mvsnet_cls_loss_from_cost(cost, depth_gt, mask, depth_value, return_prob_map=False):
+    """``mvsnet_cls_loss(softmax(cost, 1), ...)`` from the raw cost volume [B,D,H,W] of
+    ``EMVSNet(return_cost=True)`` on the HIP kernels (aarmvs.ops.cls_loss): one read of the cost
+    volume forward, one read and one write backward (p - onehot), no probability, one-hot or
+    log volume.  Same return structure: (loss, wta_depth[, max-prob confidence]).
+
+    One deviation: where a plane's probability underflows to 0 in float32 the reference's
+    0 * log(0) makes its loss NaN; this form stays finite.  CPU tensors raise AarmvsError."""
+    return _ops.cls_loss(cost, depth_gt.float(), mask.float(), depth_value.float(), return_prob_map)

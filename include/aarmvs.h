@@ -384,6 +384,49 @@ int aarmvs_deform_sample_backward(const float* x_nhwc, const float* offset, cons
                                   float* grad_mask, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * The classification loss from the cost volume (mvsnet_cls_loss of softmax(cost),
+ * drmvsnet.py:343-361, without the probability, one-hot and log volumes) and the masked depth
+ * metrics of the test pass (utils.py:150-175).  No host synchronisation, no atomics: every sum
+ * is a fixed-order fp64 reduction, so the results are bit-identical run to run.  `scratch` is
+ * aarmvs_cls_loss_scratch_bytes(B, HW) bytes of device memory (0 and an error for B, HW < 1),
+ * overwritten by each call.
+ *
+ * aarmvs_cls_loss: cost [B,D,HW] (finite values only), depth_gt / mask [B,HW], depth_values
+ * [B,D].  Per pixel: gt = round-half-even(mask * argmin_d |depth_values[d] - depth_gt|) (first
+ * minimum; clamped to [0, D-1]), lse = log sum_d exp(cost[d]), ce = lse - cost[gt].  Outputs:
+ * loss [1] = mean_b(sum mask ce / (sum mask + 1e-6)); wta_depth [B,HW] = depth_values at the
+ * first maximum of the cost; max_prob [B,HW] = max_d softmax(cost) or NULL; and for the
+ * backward lse [2,B,HW] (an fp32 pair: lse = lse[0] + lse[1]), gt_index [B,HW] (int32) and
+ * coef [B] = 1 / ((sum mask + 1e-6) B).  Only max_prob may be NULL.
+ * Deviation from the reference: where some plane's probability underflows to 0 in fp32, the
+ * reference forms 0 * log(0) = NaN for that pixel (even off the ground-truth plane) and its
+ * whole loss is NaN; this form never takes the log of a probability and stays finite.
+ *
+ * aarmvs_cls_loss_backward: grad_cost [B,D,HW] = grad_loss[0] coef[b] mask (exp(cost - lse) -
+ * [d == gt_index]) from the forward's cost, lse, gt_index, mask and coef; grad_loss is a DEVICE
+ * scalar (the upstream gradient).  No argument may be NULL; grad_cost must not alias cost.
+ *
+ * aarmvs_depth_metrics: depth_est / depth_gt / mask [B,HW]; thresholds is a HOST array of
+ * n_thresholds <= AARMVS_MAX_THRESHOLDS values (NULL if 0).  Over the pixels with mask > 0.5 of
+ * each batch element: out[0] = mean_b(mean |est - gt|) (AbsDepthError_metrics), out[1 + k] =
+ * mean_b(share with |est - gt| > thresholds[k]) (Thres_metrics); out is [1 + n_thresholds]
+ * doubles on the device.  An element with no valid pixel makes the results NaN (torch.mean of
+ * an empty tensor).
+ * ------------------------------------------------------------------------- */
+#define AARMVS_MAX_THRESHOLDS 8
+size_t aarmvs_cls_loss_scratch_bytes(int B, int HW);
+int aarmvs_cls_loss(const float* cost, const float* depth_gt, const float* mask,
+                    const float* depth_values, int B, int D, int HW, float* loss, float* wta_depth,
+                    float* max_prob, float* lse, int* gt_index, float* coef, void* scratch,
+                    hipStream_t stream);
+int aarmvs_cls_loss_backward(const float* cost, const float* lse, const int* gt_index,
+                             const float* mask, const float* coef, const float* grad_loss, int B,
+                             int D, int HW, float* grad_cost, hipStream_t stream);
+int aarmvs_depth_metrics(const float* depth_est, const float* depth_gt, const float* mask, int B,
+                         int HW, const float* thresholds, int n_thresholds, double* out,
+                         void* scratch, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Opt-in per-kernel timing (a diagnostic, not part of the reference interface).
  * When enabled, every launch made by the entry points above is bracketed by
  * hipEvents on its stream; aarmvs_profile_read synchronises on the recorded

@@ -163,6 +163,35 @@ int main() {
   f.depth_avg = reinterpret_cast<double*>(dummy);
   CHECK(aarmvs_fusion_filter(&f, nullptr) == AARMVS_ERR_INVALID);   // src_depth[1] null
 
+  // the loss and the depth metrics: null pointers, sizes below 1, more than 8 thresholds
+  CHECK(aarmvs_cls_loss_scratch_bytes(1, 64) >= 2 * sizeof(double));
+  CHECK(aarmvs_cls_loss_scratch_bytes(2, 64) == 2 * aarmvs_cls_loss_scratch_bytes(1, 64));
+  CHECK(aarmvs_cls_loss_scratch_bytes(0, 64) == 0 && has_error());
+  CHECK(aarmvs_cls_loss_scratch_bytes(1, 0) == 0 && has_error());
+  int* idummy = reinterpret_cast<int*>(dummy);
+  double* ddummy = reinterpret_cast<double*>(dummy);
+  CHECK(aarmvs_cls_loss(nullptr, dummy, dummy, dummy, 1, 4, 64, dummy, dummy, nullptr, dummy, idummy,
+                        dummy, dummy, nullptr) == AARMVS_ERR_INVALID);
+  CHECK(aarmvs_cls_loss(dummy, dummy, dummy, dummy, 1, 4, 64, dummy, dummy, nullptr, dummy, idummy,
+                        dummy, nullptr, nullptr) == AARMVS_ERR_INVALID);   // no scratch
+  CHECK(aarmvs_cls_loss(dummy, dummy, dummy, dummy, 1, 0, 64, dummy, dummy, nullptr, dummy, idummy,
+                        dummy, dummy, nullptr) == AARMVS_ERR_INVALID);     // D < 1
+  CHECK(aarmvs_cls_loss(dummy, dummy, dummy, dummy, 0, 4, 64, dummy, dummy, nullptr, dummy, idummy,
+                        dummy, dummy, nullptr) == AARMVS_ERR_INVALID);
+  CHECK(aarmvs_cls_loss_backward(dummy, dummy, idummy, dummy, dummy, nullptr, 1, 4, 64, dummy,
+                                 nullptr) == AARMVS_ERR_INVALID);          // no upstream gradient
+  CHECK(aarmvs_cls_loss_backward(dummy, dummy, idummy, dummy, dummy, dummy, 1, 4, 0, dummy,
+                                 nullptr) == AARMVS_ERR_INVALID);
+  const float thr[9] = {1, 2, 3, 4, 5, 6, 7, 8, 9};
+  CHECK(aarmvs_depth_metrics(dummy, dummy, dummy, 1, 64, thr, 9, ddummy, dummy, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_depth_metrics(dummy, dummy, dummy, 1, 64, nullptr, 2, ddummy, dummy, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_depth_metrics(dummy, dummy, nullptr, 1, 64, thr, 5, ddummy, dummy, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_depth_metrics(dummy, dummy, dummy, 1, 0, thr, 5, ddummy, dummy, nullptr) ==
+        AARMVS_ERR_INVALID);
+
   // profiling bookkeeping with nothing recorded
   const int nk = aarmvs_profile_kernel_count();
   CHECK(nk > 0);
