@@ -41,6 +41,7 @@ class SweepArgs(ctypes.Structure):
         ("omega_out", c_void_p),
         ("aux_stream", c_void_p),
         ("record", ctypes.POINTER(TrainRecord)),
+        ("record_d0", c_int), ("record_planes", c_int),
     ]
 
 
@@ -62,6 +63,7 @@ class BackwardArgs(ctypes.Structure):
         ("workspace", c_void_p),
         ("scratch", c_void_p),
         ("regulariser_only", c_int),
+        ("d_begin", c_int), ("d_end", c_int), ("record_d0", c_int), ("record_planes", c_int),
     ]
 
 
@@ -120,6 +122,7 @@ SIGNATURES = {
     "aarmvs_sweep": (c_int, [ctypes.POINTER(SweepArgs), c_void_p]),
     "aarmvs_aux_stream": (c_int, [ctypes.POINTER(c_void_p)]),
     "aarmvs_train_record_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "aarmvs_train_segment_bytes": (c_int, [c_int] * 5 + [ctypes.POINTER(c_size_t)] * 2),
     "aarmvs_backward_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "aarmvs_sweep_backward": (c_int, [ctypes.POINTER(BackwardArgs), c_void_p]),
     "aarmvs_state_ptr": (c_void_p, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

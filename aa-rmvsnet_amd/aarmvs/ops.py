@@ -554,13 +554,42 @@ class DepthSweep:
         return out
 
     @staticmethod
-    def record_buffers(B: int, H: int, W: int, D: int, device, *, nsrc: int) -> dict:
+    def record_buffers(B: int, H: int, W: int, D: int, device, *, nsrc: int, planes: int | None = None) -> dict:
         """Device buffers of a training record (aarmvs_train_record) for D planes and nsrc
         source views: the cost slices, D + 1 regulariser state slabs, the gate pre-activations,
         the deconv outputs and their GroupNorm statistics, the omega conv output and its
-        statistics (~1 KB per pixel and plane at B = 1, N = 3)."""
+        statistics (~1 KB per pixel and plane at B = 1, N = 3).  ``planes``: a segment record of
+        that many planes (at most D) instead, for ``record_d0`` calls (plane-segment
+        checkpointing; ``record_bytes`` gives the sizes)."""
+        n_planes = D if planes is None else int(planes)
+        if not 1 <= n_planes <= D:
+            raise AarmvsError(f"aarmvs: a segment record holds 1..D={D} planes, got {planes}")
         return {k: torch.empty(n, dtype=torch.uint8, device=device)
-                for k, n in DepthSweep._record_sizes(B, H, W, D, nsrc).items()}
+                for k, n in DepthSweep._record_sizes(B, H, W, n_planes, nsrc).items()}
+
+    @staticmethod
+    def record_bytes(B: int, H: int, W: int, planes: int, *, nsrc: int) -> tuple:
+        """(bytes of a record of ``planes`` planes, bytes of one state checkpoint), from
+        aarmvs_train_segment_bytes.  No device needed."""
+        rec, ck = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        check(lib().aarmvs_train_segment_bytes(B, H, W, nsrc, planes, ctypes.byref(rec), ctypes.byref(ck)),
+              "train_segment_bytes")
+        return int(rec.value), int(ck.value)
+
+    @staticmethod
+    def _record_planes(rec: dict, B: int, H: int, W: int, nsrc: int) -> int:
+        """The planes a record's buffers have room for (the smallest over the seven)."""
+        L = lib()
+        planes = None
+        for i, name in enumerate(DepthSweep.RECORD_KEYS):
+            slab = L.aarmvs_train_record_bytes(B, H, W, i)
+            t = rec.get(name)
+            if slab == 0 or t is None:
+                raise AarmvsError(f"aarmvs: training record '{name}' missing or invalid geometry B={B} H={H} W={W}")
+            n = t.numel() * t.element_size() // slab
+            n = n - 1 if name == "state" else n // nsrc if name in ("t1", "ostats") else n
+            planes = n if planes is None else min(planes, n)
+        return planes
 
     @staticmethod
     def _record_struct(rec: dict, B: int, H: int, W: int, D: int, nsrc: int, device=None):
@@ -577,10 +606,27 @@ class DepthSweep:
         (r.x, r.state, r.z, r.u, r.stats, r.t1, r.ostats) = (rec[k].data_ptr() for k in DepthSweep.RECORD_KEYS)
         return r
 
+    def _segment_struct(self, a, record: dict, record_d0, d0: int, d1: int, device):
+        """Points ``a`` (SweepArgs or BackwardArgs with its geometry set) at ``record`` as the
+        record of the planes from ``record_d0`` on, after checking that the buffers hold the
+        planes d0..d1-1 of the call; returns the ctypes record (to be kept alive)."""
+        record_d0 = int(record_d0)
+        if not 0 <= record_d0 < a.D:
+            raise AarmvsError(f"aarmvs: record_d0 {record_d0} outside [0, D={a.D})")
+        n = min(self._record_planes(record, a.B, a.H, a.W, a.nsrc), a.D - record_d0)
+        if n < 1 or d0 < record_d0 or d1 > record_d0 + n:
+            raise AarmvsError(f"aarmvs: the training record holds planes [{record_d0}, {record_d0 + max(n, 0)}) "
+                              f"and does not cover the range [{d0}, {d1}) (record_buffers(B, H, W, D, "
+                              f"nsrc={a.nsrc}[, planes=S]) and record_d0)")
+        rs = self._record_struct(record, a.B, a.H, a.W, n, a.nsrc, device)
+        a.record = ctypes.pointer(rs)
+        a.record_d0, a.record_planes = record_d0, n
+        return rs
+
     @_on_tensor_device
     def __call__(self, ref_fea, src_feas, ref_proj, src_projs, depth_values, *,
                  want_depth=True, want_cost=False, d_range=None, debug=False, cost_out=None,
-                 rel=None, record=None):
+                 rel=None, record=None, record_d0=0):
         """Returns dict(depth, conf, cost, slice, omega) (entries None when not requested).
 
         ``d_range=(d0, d1)`` runs planes d0..d1-1 only (d0 == 0 resets the hidden state;
@@ -588,7 +634,10 @@ class DepthSweep:
         ``cost_out`` is an optional caller-owned [B,D,H,W] buffer for the regulariser output.
         ``rel`` is an optional precomputed ``self.relative(ref_proj, src_projs, B)``.
         ``record`` (``record_buffers(B, H, W, D, nsrc=...)``) keeps every plane's tensors for
-        ``backward`` (the training forward).
+        ``backward`` (the training forward).  ``record_d0``: ``record`` is a segment record
+        (``record_buffers(..., planes=S)``) whose slab i is plane ``record_d0 + i``; the call's
+        planes must lie inside it, and it starts from the state in the record's state slab
+        ``d0 - record_d0`` (the caller's checkpoint; zeroed by the library when d0 == 0).
         """
         ref = ref_fea.contiguous()
         srcs = [s.contiguous() for s in src_feas]
@@ -649,19 +698,29 @@ class DepthSweep:
         a.aux_stream = self._aux.cuda_stream if self._aux is not None else None
         rec_struct = None
         if record is not None:
-            rec_struct = self._record_struct(record, B, H, W, D, nsrc, ref.device)
-            a.record = ctypes.pointer(rec_struct)
+            rec_struct = self._segment_struct(a, record, record_d0, d0, d1, ref.device)
+        elif record_d0:
+            raise AarmvsError("aarmvs: record_d0 without a record")
         check(lib().aarmvs_sweep(ctypes.byref(a), _stream()), "sweep")
         out["_keepalive"] = (rel, dv, srcs, ref, rec_struct)
         return out
 
     @_on_tensor_device
     def backward(self, ref_fea, src_feas, rel, depth_values, record, grad_cost, *,
-                 regulariser_only=False, want_grad_x=False):
+                 regulariser_only=False, want_grad_x=False, d_range=None, record_d0=0, grad_x_out=None):
         """Backward of a recorded training sweep (aarmvs_sweep_backward): from dL/dcost
         [B,D,H,W] to (grad_ref [B,32,H,W], [grad_src [B,32,H,W]] per view, {sweep parameter
         name: gradient}, grad_x [D,B,H,W,32] NHWC or None).  ``regulariser_only`` stops after
-        the regulariser (debug: grad_ref/grad_src are None, the omega.* gradients zero)."""
+        the regulariser (debug: grad_ref/grad_src are None, the omega.* gradients zero).
+
+        ``d_range=(d0, d1)`` runs the planes d0..d1-1 only, on a ``record`` that holds the planes
+        from ``record_d0`` on (a segment record).  d0 and d1 must be multiples of 16 (d1 may be
+        D).  One backward is a chain of such calls, last range first (d1 == D), each ending
+        where the one before began, down to d0 == 0; only the recompute forward of the next
+        segment may use this object in between.  The calls before the final one return None; the
+        final one (d0 == 0) returns the gradients of the whole sweep, bit for bit those of one
+        call on a whole record.  ``grad_x_out``: a caller-owned [D,B,H,W,32] buffer for grad_x
+        (each call fills its planes)."""
         ref = ref_fea.contiguous()
         srcs = [t.contiguous() for t in src_feas]
         _require_device(ref, *srcs, grad_cost)
@@ -672,20 +731,41 @@ class DepthSweep:
         g = grad_cost.contiguous()
         if tuple(g.shape) != (B, D, H, W):
             raise AarmvsError(f"aarmvs: grad_cost must be [B={B},D={D},H={H},W={W}], got {tuple(g.shape)}")
+        d0, d1 = (0, D) if d_range is None else (int(d_range[0]), int(d_range[1]))
+        if not 0 <= d0 < d1 <= D:
+            raise AarmvsError(f"aarmvs: bad backward d_range {d_range} for D={D}")
         ws = self.workspace(B, H, W, nsrc)
         L = lib()
         key = ("bwd", B, H, W, nsrc)
         scratch = self._ws.get(key)
+        # a call that continues a backward needs the scratch the call before it left: the same
+        # buffer, and the range that ends where that one began
+        chain = getattr(self, "_bwd_chain", None)
+        self._bwd_chain = None
+        if d1 != D and (scratch is None or chain != (key, d1, bool(regulariser_only))):
+            raise AarmvsError(f"aarmvs: backward over [{d0}, {d1}) does not continue a backward of this "
+                              f"geometry that stopped at plane {d1} (the calls come last range first, "
+                              "contiguous, with nothing but the recompute forward between them)")
         if scratch is None:
             n = L.aarmvs_backward_scratch_bytes(B, H, W, nsrc)
             if n == 0:
                 raise AarmvsError(f"aarmvs: invalid backward geometry B={B} H={H} W={W} nsrc={nsrc}")
             scratch = torch.empty(n, dtype=torch.uint8, device=ref.device)
             self._ws[key] = scratch
-        grad_ref = None if regulariser_only else torch.empty_like(ref)
-        grad_src = None if regulariser_only else [torch.empty_like(t) for t in srcs]
-        grad_params = torch.empty(L.aarmvs_param_count(), device=ref.device)
-        grad_x = torch.empty(D, B, H, W, C, device=ref.device) if want_grad_x else None
+        final = d0 == 0
+        grad_ref = torch.empty_like(ref) if final and not regulariser_only else None
+        grad_src = [torch.empty_like(t) for t in srcs] if final and not regulariser_only else None
+        grad_params = torch.empty(L.aarmvs_param_count(), device=ref.device) if final else None
+        grad_x = None
+        if grad_x_out is not None:
+            _require_device(grad_x_out)
+            if tuple(grad_x_out.shape) != (D, B, H, W, C) or not grad_x_out.is_contiguous():
+                raise AarmvsError(f"aarmvs: grad_x_out must be a contiguous [D={D},B,H,W,{C}] tensor")
+            grad_x = grad_x_out
+        elif want_grad_x:
+            if (d0, d1) != (0, D):
+                raise AarmvsError("aarmvs: a ranged backward returns grad_x through grad_x_out")
+            grad_x = torch.empty(D, B, H, W, C, device=ref.device)
         a = _lib.BackwardArgs()
         a.B, a.C, a.H, a.W, a.nsrc, a.D = B, C, H, W, nsrc, D
         a.ref_fea = ref.data_ptr()
@@ -701,16 +781,20 @@ class DepthSweep:
             raise AarmvsError(f"aarmvs: rel must be a contiguous float32 [nsrc={nsrc}, B={B}, 12] tensor on "
                               f"{ref.device} (DepthSweep.relative), got "
                               f"{tuple(rel.shape) if torch.is_tensor(rel) else type(rel)}")
-        rs = self._record_struct(record, B, H, W, D, nsrc, ref.device)
-        a.record = ctypes.pointer(rs)
+        rs = self._segment_struct(a, record, record_d0, d0, d1, ref.device)
+        a.d_begin, a.d_end = d0, d1
         a.grad_cost = g.data_ptr()
         a.grad_ref = _ptr(grad_ref)
-        a.grad_params = grad_params.data_ptr()
+        a.grad_params = _ptr(grad_params)
         a.grad_x = _ptr(grad_x)
         a.workspace = ws.data_ptr()
         a.scratch = scratch.data_ptr()
         a.regulariser_only = 1 if regulariser_only else 0
         check(L.aarmvs_sweep_backward(ctypes.byref(a), _stream()), "sweep_backward")
+        del rs
+        if not final:
+            self._bwd_chain = (key, d0, bool(regulariser_only))
+            return None
         grads, off = {}, 0
         for k in SWEEP_KEYS:
             n = 1

@@ -71,6 +71,10 @@ def parse_args(argv=None):
     ap.add_argument("--fused_loss", action="store_true",
                     help="loss from the raw cost volume on the HIP kernels (where the evidential "
                          "head does not run)")
+    ap.add_argument("--checkpoint_planes", type=int, default=0,
+                    help="plane-segment checkpointing of the sweep's BPTT: keep a record of this many "
+                         "planes (a multiple of 16) and recompute each segment's forward before its "
+                         "backward; same gradients, bit for bit (0: the whole record)")
     ap.add_argument("--testpath", default=None, help="test datapath: run train.py's per-epoch test pass")
     ap.add_argument("--testlist", default=None, help="test list")
     ap.add_argument("--test_light_idx", type=int, default=3,
@@ -147,7 +151,8 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
         shard = torch.utils.data.Subset(tds, list(shard_range(len(tds), rank, world)))
         test_loader = DataLoader(shard, args.batch_size, shuffle=False, num_workers=0, drop_last=False)
     model = EMVSNet(disparity_level=args.numdepth, image_scale=args.image_scale,
-                    max_h=args.max_h, max_w=args.max_w, return_cost=args.fused_loss)
+                    max_h=args.max_h, max_w=args.max_w, return_cost=args.fused_loss,
+                    checkpoint_planes=args.checkpoint_planes)
     if args.loadckpt:   # train.py:150-170: tensors only, any 'module.' prefix removed
         state = torch.load(args.loadckpt, map_location="cpu", weights_only=True)["model"]
         model.load_state_dict(_strip_module(state), strict=True)

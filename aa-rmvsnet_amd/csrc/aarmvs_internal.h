@@ -322,6 +322,12 @@ struct StreamJoin {
 // gx [n][B][H][W][32]) and copied to grad_x if set.
 struct BpttRun {
   int B, H, W, D;
+  // The planes of this call, [d_begin, d_end): multiples of kPlaneGroup (d_end may be D), so
+  // that the groups are those of the whole backward.  One backward is a chain of calls, last
+  // range first: the one with d_end == D zeroes the state gradients and the accumulators in
+  // `scratch`, the others continue from what the call before left there, and the one with
+  // d_begin == 0 writes grad_params.  `rec` is indexed by the absolute plane.
+  int d_begin, d_end;
   const float* packed;
   const aarmvs_train_record* rec;
   const float* grad_cost;      // [B][D][H][W]

@@ -547,6 +547,22 @@ size_t aarmvs_train_record_bytes(int B, int H, int W, int which) {
   }
 }
 
+int aarmvs_train_segment_bytes(int B, int H, int W, int nsrc, int planes, size_t* record_bytes,
+                               size_t* checkpoint_bytes) {
+  int rc = check_geom(B, H, W, nsrc);
+  if (rc) return rc;
+  if (planes < 1) return fail(AARMVS_ERR_INVALID, "train_segment_bytes: planes must be >= 1");
+  const size_t n = (size_t)planes;
+  size_t total = 0;
+  for (int which = 0; which < 7; ++which) {
+    const size_t slabs = which == 1 ? n + 1 : which >= 5 ? n * nsrc : n;
+    total += slabs * aarmvs_train_record_bytes(B, H, W, which);
+  }
+  if (record_bytes) *record_bytes = total;
+  if (checkpoint_bytes) *checkpoint_bytes = aarmvs_train_record_bytes(B, H, W, 1);
+  return AARMVS_OK;
+}
+
 int aarmvs_aux_stream(hipStream_t* out) {
   if (!out) return fail(AARMVS_ERR_INVALID, "aux_stream: null out");
   int dev = 0;
@@ -599,6 +615,55 @@ hipError_t aarmvs::library_stream(int dev, int i, hipStream_t& out) {
   }
   out = pool[dev][i];
   return hipSuccess;
+}
+
+// The plane range of a call against the planes its record holds (include/aarmvs.h, "Segment
+// records"): record_d0 / record_planes as given (0 planes: up to D).
+static int check_record_range(const std::string& who, int D, int d_begin, int d_end, int rec_d0, int rec_n) {
+  if (rec_d0 < 0 || rec_n < 0 || rec_d0 >= D || rec_d0 + rec_n > D)
+    return fail(AARMVS_ERR_INVALID, who + ": the record's planes (record_d0 " + std::to_string(rec_d0) +
+                                        ", record_planes " + std::to_string(rec_n) + ") lie outside [0, D = " +
+                                        std::to_string(D) + "]");
+  const int rec_end = rec_n ? rec_d0 + rec_n : D;
+  if (d_begin < rec_d0 || d_end > rec_end)
+    return fail(AARMVS_ERR_INVALID, who + ": the record holds planes [" + std::to_string(rec_d0) + ", " +
+                                        std::to_string(rec_end) + ") and does not cover the range [" +
+                                        std::to_string(d_begin) + ", " + std::to_string(d_end) + ")");
+  return AARMVS_OK;
+}
+
+// A segment record addressed as a whole one: every buffer's base moved back by d0 slabs, so that
+// plane d's slab sits at index d, as the sweep, the BPTT and the cost-slice backward index it.
+// Only the slabs of planes the record holds are ever formed into addresses that are used
+// (check_record_range); the moved bases themselves are never dereferenced.
+static aarmvs_train_record rebase_record(const aarmvs_train_record& r, const TrainLayout& T, const Workspace& ws,
+                                         int d0) {
+  aarmvs_train_record v = r;
+  if (d0 == 0) return v;
+  const ptrdiff_t d = d0;
+  v.x = r.x - d * (ptrdiff_t)T.x_plane;
+  v.state = r.state - d * (ptrdiff_t)T.state_slab;
+  v.z = r.z - d * (ptrdiff_t)T.z_slab;
+  v.u = r.u - d * (ptrdiff_t)T.u_slab;
+  v.stats = r.stats - d * (ptrdiff_t)T.stats_slab;
+  v.t1 = r.t1 - d * (ptrdiff_t)(ws.t1_plane * 4);
+  v.ostats = r.ostats - d * (ptrdiff_t)(ws.omega_stats_bytes / sizeof(double));
+  return v;
+}
+
+// the c8 feature copies of the cost stage; each copy also folds 8 max|feature|^2 into ws.xbound
+// (cell 0's fp16 range guard), zeroed first
+static int make_feature_copies(const std::string& who, const float* ref, const float* const* src, int nsrc, int B,
+                               int HW, const Workspace& ws, hipStream_t stream) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(ws.xbound, 0, sizeof(unsigned), stream)) != hipSuccess)
+    return hip_fail(e, (who + ": bound init").c_str());
+  if ((e = launch_to_c8(ref, ws.feat8[0], B, HW, stream, ws.xbound)) != hipSuccess)
+    return hip_fail(e, (who + ": c8 copy").c_str());
+  for (int v = 0; v < nsrc; ++v)
+    if ((e = launch_to_c8(src[v], ws.feat8[1 + v], B, HW, stream, ws.xbound)) != hipSuccess)
+      return hip_fail(e, (who + ": c8 copy").c_str());
+  return AARMVS_OK;
 }
 
 // walk_sweep's sink: one sweep call's launches, event records and event waits on HIP
@@ -704,10 +769,20 @@ int aarmvs_sweep(const aarmvs_sweep_args* a, hipStream_t stream) {
   const aarmvs_train_record* rec = a->record;
   if (rec && (!rec->x || !rec->state || !rec->z || !rec->u || !rec->stats || !rec->t1 || !rec->ostats))
     return fail(AARMVS_ERR_INVALID, "sweep: training record with a null buffer");
+  if (rec && (rc = check_record_range("sweep", a->D, a->d_begin, a->d_end, a->record_d0, a->record_planes)))
+    return rc;
   const TrainLayout T = train_layout(a->B, a->H, a->W);
 
   SweepGeom g{a->B, a->H, a->W, a->nsrc, a->D, cu_count()};
   Workspace ws = carve_workspace(a->workspace, a->B, a->H, a->W, a->nsrc);
+  // a segment record is addressed by the absolute plane from here on
+  aarmvs_train_record rec_abs{};
+  aarmvs_sweep_args a_abs = *a;
+  if (rec) {
+    rec_abs = rebase_record(*rec, T, ws, a->record_d0);
+    a_abs.record = rec = &rec_abs;
+    a = &a_abs;
+  }
   const float* params = static_cast<const float*>(a->packed_params);
   hipError_t e;
   CostArgs ca{};
@@ -768,6 +843,16 @@ int aarmvs_sweep(const aarmvs_sweep_args* a, hipStream_t stream) {
       if ((e = launch_to_c8(a->src_fea[v], ws.feat8[1 + v], a->B, HW, stream, ws.xbound)) !=
           hipSuccess)
         return hip_fail(e, "sweep: c8 copy");
+  } else if (rec) {
+    // A recorded call that starts inside the sweep (a later d_range piece, or the recompute of a
+    // checkpointed segment) stands on its own: of what the d_begin == 0 branch prepares, record
+    // mode reads the state from the record (slab d_begin - record_d0, the caller's), takes its
+    // statistics in the record (zeroed below and per group in launch_omega_group) and needs the
+    // WTA images only for depth_out / conf_out; what is left are the c8 feature copies and the
+    // guard bound, re-made here as aarmvs_sweep_backward does (the workspace may have served
+    // another sweep since; the same values when it has not)
+    if ((rc = make_feature_copies("sweep", a->ref_fea, a->src_fea, a->nsrc, a->B, a->H * a->W, ws, stream)))
+      return rc;
   }
   // a record's statistics slabs accumulate from zero (block 0 of cells 3 and 4 fills slot 0 of each)
   if (rec && (e = hipMemsetAsync(rec->stats + (size_t)a->d_begin * T.stats_slab, 0,
@@ -801,20 +886,33 @@ int aarmvs_sweep_backward(const aarmvs_backward_args* a, hipStream_t stream) {
     return fail(AARMVS_ERR_INVALID, "sweep_backward: training record with a null buffer");
   for (int v = 0; v < a->nsrc; ++v)
     if (!a->src_fea[v]) return fail(AARMVS_ERR_INVALID, "sweep_backward: null src_fea pointer");
-  if (!a->regulariser_only && !a->grad_ref)
+  // (written by the call that ends a backward, d_begin == 0; the earlier calls of a ranged one
+  // do not touch the outputs)
+  if (!a->regulariser_only && !a->grad_ref && a->d_begin == 0)
     return fail(AARMVS_ERR_INVALID, "sweep_backward: grad_ref is required (the cost-slice part)");
+  // the plane range of this call (all zero: the whole backward)
+  const int d_begin = a->d_begin, d_end = a->d_end ? a->d_end : a->D;
+  if (d_begin < 0 || d_end > a->D || d_begin >= d_end)
+    return fail(AARMVS_ERR_INVALID, "sweep_backward: the range [" + std::to_string(d_begin) + ", " +
+                                        std::to_string(d_end) + ") lies outside [0, D = " + std::to_string(a->D) +
+                                        "] or is empty (need 0 <= d_begin < d_end <= D)");
+  if (d_begin % kPlaneGroup || (d_end % kPlaneGroup && d_end != a->D))
+    return fail(AARMVS_ERR_INVALID, "sweep_backward: misaligned range [" + std::to_string(d_begin) + ", " +
+                                        std::to_string(d_end) + "): d_begin and d_end must be multiples of " +
+                                        std::to_string(kPlaneGroup) + " (d_end may equal D), so that the groups "
+                                        "are the whole backward's");
+  if ((rc = check_record_range("sweep_backward", a->D, d_begin, d_end, a->record_d0, a->record_planes))) return rc;
   Workspace ws = carve_workspace(a->workspace, a->B, a->H, a->W, a->nsrc);
   hipError_t e;
+  // a segment record is addressed by the absolute plane from here on
+  const aarmvs_train_record rec_abs = rebase_record(*rec, train_layout(a->B, a->H, a->W), ws, a->record_d0);
+  aarmvs_backward_args a_abs = *a;
+  a_abs.record = rec = &rec_abs;
+  a = &a_abs;
   // the c8 feature copies and the fp16 guard bound of the forward, recomputed (the workspace
   // may have served another sweep since)
-  const int HW = a->H * a->W;
-  if ((e = hipMemsetAsync(ws.xbound, 0, sizeof(unsigned), stream)) != hipSuccess)
-    return hip_fail(e, "sweep_backward: bound init");
-  if ((e = launch_to_c8(a->ref_fea, ws.feat8[0], a->B, HW, stream, ws.xbound)) != hipSuccess)
-    return hip_fail(e, "sweep_backward: c8 copy");
-  for (int v = 0; v < a->nsrc; ++v)
-    if ((e = launch_to_c8(a->src_fea[v], ws.feat8[1 + v], a->B, HW, stream, ws.xbound)) != hipSuccess)
-      return hip_fail(e, "sweep_backward: c8 copy");
+  if ((rc = make_feature_copies("sweep_backward", a->ref_fea, a->src_fea, a->nsrc, a->B, a->H * a->W, ws, stream)))
+    return rc;
   char* scratch = static_cast<char*>(a->scratch);
   const size_t breg = bptt_scratch_bytes(a->B, a->H, a->W);
   CostBwdCtx cctx{};
@@ -822,13 +920,18 @@ int aarmvs_sweep_backward(const aarmvs_backward_args* a, hipStream_t stream) {
   cctx.ws = ws;
   cctx.scratch = scratch + breg;
   cctx.gacc = bptt_gacc(scratch, a->B, a->H, a->W);
-  if (!a->regulariser_only && (e = cost_bwd_begin(cctx, stream)) != hipSuccess)
+  // the first call of a backward (its last planes) zeroes what the calls carry in `scratch`
+  // (here the cost-slice accumulators, in bptt_regulariser the state gradients and gacc), the
+  // last one (d_begin == 0) folds them into the outputs
+  if (!a->regulariser_only && d_end == a->D && (e = cost_bwd_begin(cctx, stream)) != hipSuccess)
     return hip_fail(e, "sweep_backward: cost-slice init");
   BpttRun r{};
   r.B = a->B;
   r.H = a->H;
   r.W = a->W;
   r.D = a->D;
+  r.d_begin = d_begin;
+  r.d_end = d_end;
   r.packed = static_cast<const float*>(a->packed_params);
   r.rec = rec;
   r.grad_cost = a->grad_cost;
@@ -839,7 +942,7 @@ int aarmvs_sweep_backward(const aarmvs_backward_args* a, hipStream_t stream) {
   r.group_done = a->regulariser_only ? nullptr : cost_bwd_group;
   r.ctx = &cctx;
   if ((e = bptt_regulariser(r, stream)) != hipSuccess) return hip_fail(e, "sweep_backward");
-  if (!a->regulariser_only && (e = cost_bwd_end(cctx, stream)) != hipSuccess)
+  if (!a->regulariser_only && d_begin == 0 && (e = cost_bwd_end(cctx, stream)) != hipSuccess)
     return hip_fail(e, "sweep_backward: cost-slice gradients");
   return AARMVS_OK;
 }

@@ -1441,12 +1441,15 @@ hipError_t bptt_regulariser(const BpttRun& r, hipStream_t s) {
   do {                                    \
     if ((e = (x)) != hipSuccess) return e; \
   } while (0)
-  // state gradients start at zero after the last plane; parameter accumulators at zero
-  for (int k = 0; k < 5; ++k) {
-    CK(hipMemsetAsync(L.gh[k], 0, L.cell_px[k] * kCellHid[k] * 4, s));
-    CK(hipMemsetAsync(L.gc[k], 0, L.cell_px[k] * kCellHid[k] * 4, s));
+  // state gradients start at zero after the last plane; parameter accumulators at zero (a later
+  // call of a ranged backward goes on from the gh, gc and gacc the call before it left)
+  if (r.d_end == D) {
+    for (int k = 0; k < 5; ++k) {
+      CK(hipMemsetAsync(L.gh[k], 0, L.cell_px[k] * kCellHid[k] * 4, s));
+      CK(hipMemsetAsync(L.gc[k], 0, L.cell_px[k] * kCellHid[k] * 4, s));
+    }
+    CK(hipMemsetAsync(L.gacc, 0, PL.raw_total * 8, s));
   }
-  CK(hipMemsetAsync(L.gacc, 0, PL.raw_total * 8, s));
   const int res_div[5] = {1, 2, 4, 2, 1};
   auto zslot = [&](int k, int slot) { return L.gz[k] + (size_t)slot * L.cell_px[k] * 4 * kCellHid[k]; };
   // blocks of cell k's gate kernel (run_gate_bwd): hid / 4 threads per cell pixel
@@ -1601,7 +1604,7 @@ hipError_t bptt_regulariser(const BpttRun& r, hipStream_t s) {
     CK(hipMalloc(&g_trace, (size_t)D * kTraceSlots * 8));
     g_trace_planes = D;
   }
-  if (trace) CK(hipMemsetAsync(g_trace, 0, (size_t)D * kTraceSlots * 8, s));
+  if (trace && r.d_end == D) CK(hipMemsetAsync(g_trace, 0, (size_t)D * kTraceSlots * 8, s));
   auto tr = [&](hipStream_t st, int d, int slot, const void* ptr, size_t nfloats) -> hipError_t {
     if (!trace) return hipSuccess;
     hipLaunchKernelGGL(cksum_kernel, dim3(1), dim3(256), 0, st, static_cast<const unsigned*>(ptr), nfloats,
@@ -1612,8 +1615,9 @@ hipError_t bptt_regulariser(const BpttRun& r, hipStream_t s) {
   auto zsz = [&](int k) { return L.cell_px[k] * 4 * kCellHid[k]; };
   auto hsz = [&](int k) { return L.cell_px[k] * kCellHid[k]; };
   int gi = 0;
-  for (int g0 = ((D - 1) / G) * G; g0 >= 0; g0 -= G, ++gi) {
-    const int n = std::min(G, D - g0);
+  // (the groups start at multiples of G whatever the call's range: the whole backward's groups)
+  for (int g0 = ((r.d_end - 1) / G) * G; g0 >= r.d_begin; g0 -= G, ++gi) {
+    const int n = std::min(G, r.d_end - g0);
     L.use_set(gi & 1);
     if (sg != s && gi >= 2) CK(xwait(s, evG[gi & 1]));   // set free again
     if (sa != s) {   // the aux stream starts after everything the group's stage A overwrites is consumed
@@ -1838,7 +1842,7 @@ hipError_t bptt_regulariser(const BpttRun& r, hipStream_t s) {
     if (pipe_mode == 4 && sg != s) CK(xwait(s, evG[gi & 1]));
   }
   CK(join_g.join());
-  if (r.grad_params) {
+  if (r.grad_params && r.d_begin == 0) {
     hipLaunchKernelGGL(gacc_to_float_kernel, dim3(256), dim3(256), 0, s, L.gacc, r.grad_params,
                        PL.raw_total);
     CK(hipGetLastError());

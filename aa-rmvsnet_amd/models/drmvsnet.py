@@ -21,6 +21,8 @@ What runs where:
   training record (~1 KB/px/plane instead of the reference's ~2.3 KB/px/plane of autograd
   activations); the backward (BPTT through every plane, the omega/warp backward and all
   parameter gradients) is the library's aarmvs_sweep_backward.
+  ``EMVSNet(..., checkpoint_planes=S)`` keeps an S-plane record instead and recomputes each
+  S-plane segment's forward before its backward (the same gradients bit for bit).
 * The evidential head (evidential/models.py) is this package's PyTorch
   restatement ``evidential.models.EvidentialModule``, attached by default with the
   reference's 221 ``evidential.*`` keys (311 keys in all, as the reference: its shipped
@@ -240,6 +242,87 @@ class _SweepTrain(torch.autograd.Function):
         return (None, None, None, None, None, g_ref, *g_srcs, *g_params)
 
 
+def _raw_copy(dst: torch.Tensor, src: torch.Tensor) -> None:
+    """dst.copy_(src) without touching dst's autograd version counter (the record buffers are
+    saved tensors that the library rewrites in place anyway; autograd must not take the
+    checkpoint restore for a stale-tensor hazard: ctx.holds tracks what the buffers hold)."""
+    dst.data.copy_(src)
+
+
+class _SweepTrainCkpt(torch.autograd.Function):
+    """_SweepTrain with plane-segment checkpointing (``EMVSNet(checkpoint_planes=S)``): the
+    same cost volume and, bit for bit, the same gradients from ONE S-plane record.
+
+    Forward: the recorded sweep runs segment by segment ([0,S), [S,2S), ...) into the same
+    S-plane record (DepthSweep record_d0); after each segment but the last, its final state slab
+    (264 B per pixel) is copied out as the checkpoint "state before the next segment" and into
+    state slab 0 for it.  The record keeps the last segment.  Backward, segments last to first:
+    the checkpoint goes back into state slab 0, the segment's recorded forward runs again
+    (unless the record still holds that segment) and DepthSweep.backward(d_range=segment)
+    continues the BPTT; the call of segment 0 returns the gradients.  The record costs
+    S / D of _SweepTrain's, the step one more recorded forward of all but the last segment.
+
+    ctx.holds is the index of the segment the record holds, so a second backward through a
+    retained graph recomputes what the first one overwrote (the same gradients again)."""
+
+    @staticmethod
+    def _segments(D: int, S: int):
+        return [(s0, min(s0 + S, D)) for s0 in range(0, D, S)]
+
+    @staticmethod
+    def forward(ctx, model, sweep, S, ref_proj, src_projs, depth_values, ref, *rest):
+        nsrc = len(src_projs)
+        srcs, params = list(rest[:nsrc]), rest[nsrc:]
+        B, C, H, W = ref.shape
+        D = depth_values.shape[1]
+        segs = _SweepTrainCkpt._segments(D, S)
+        cost = torch.empty(B, D, H, W, device=ref.device)
+        rel = sweep.relative(ref_proj, src_projs, B)
+        rec = sweep.record_buffers(B, H, W, D, ref.device, nsrc=nsrc, planes=min(S, D))
+        slab = sweep.record_bytes(B, H, W, 1, nsrc=nsrc)[1]
+        ckpts = []   # ckpts[i - 1]: the state before segment i
+        for s0, s1 in segs:
+            sweep(ref, srcs, ref_proj, src_projs, depth_values, want_depth=False, cost_out=cost,
+                  rel=rel, record=rec, record_d0=s0, d_range=(s0, s1))
+            if s1 < D:
+                ckpts.append(rec["state"][(s1 - s0) * slab:(s1 - s0 + 1) * slab].clone())
+                rec["state"][:slab].copy_(ckpts[-1])
+        ctx.sweep = sweep
+        ctx.nsrc = nsrc
+        ctx.segs = segs
+        ctx.slab = slab
+        ctx.holds = len(segs) - 1
+        ctx.save_for_backward(ref, *srcs, rel, depth_values, *ckpts,
+                              *(rec[k] for k in _ops.DepthSweep.RECORD_KEYS))
+        return cost
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_cost):
+        saved = ctx.saved_tensors
+        nsrc, segs, slab, sweep = ctx.nsrc, ctx.segs, ctx.slab, ctx.sweep
+        ref, srcs = saved[0], list(saved[1:1 + nsrc])
+        rel, dv = saved[1 + nsrc], saved[2 + nsrc]
+        nck = len(segs) - 1
+        ckpts = saved[3 + nsrc:3 + nsrc + nck]
+        rec = dict(zip(_ops.DepthSweep.RECORD_KEYS, saved[3 + nsrc + nck:]))
+        grad_cost = grad_cost.contiguous()
+        out = None
+        for i in range(len(segs) - 1, -1, -1):
+            s0, s1 = segs[i]
+            if ctx.holds != i:
+                ctx.holds = -1   # (an error below leaves the record marked as holding nothing)
+                if i > 0:
+                    _raw_copy(rec["state"][:slab], ckpts[i - 1])
+                sweep(ref, srcs, None, [None] * nsrc, dv, want_depth=False, rel=rel, record=rec,
+                      record_d0=s0, d_range=(s0, s1))
+                ctx.holds = i
+            out = sweep.backward(ref, srcs, rel, dv, rec, grad_cost, d_range=(s0, s1), record_d0=s0)
+        g_ref, g_srcs, g_par, _ = out
+        g_params = [g_par[k] for k in _ops.SWEEP_KEYS]
+        return (None, None, None, None, None, None, g_ref, *g_srcs, *g_params)
+
+
 class _SoftmaxDepth(torch.autograd.Function):
     """softmax over dim 1 of [B,D,H,W] (drmvsnet.py:291/:342) on the HIP kernel."""
 
@@ -264,8 +347,17 @@ class EMVSNet(nn.Module):
                      "warp gather/scatter) on gfx950")
 
     def __init__(self, disparity_level, image_scale=0.25, max_h=960, max_w=480, return_depth=False,
-                 evidential=True, return_cost=False):
+                 evidential=True, return_cost=False, checkpoint_planes=0):
         super().__init__()
+        # plane-segment checkpointing of the training sweep (_SweepTrainCkpt): 0 keeps the whole
+        # record (_SweepTrain); S > 0 keeps an S-plane record and recomputes each segment's
+        # forward before its backward.  Multiples of 16 only: the backward's 16-plane groups must
+        # stay those of the whole backward for the gradients to be bit-identical.
+        checkpoint_planes = int(checkpoint_planes)
+        if checkpoint_planes < 0 or checkpoint_planes % 16:
+            raise ValueError(f"EMVSNet: checkpoint_planes must be 0 or a positive multiple of 16, "
+                             f"got {checkpoint_planes}")
+        self.checkpoint_planes = checkpoint_planes
         self.feature = FeatNet()
         input_size = (int(max_h * image_scale), int(max_w * image_scale))
         num_layers = 5
@@ -324,7 +416,10 @@ class EMVSNet(nn.Module):
             need_grad = torch.is_grad_enabled() and (
                 ref.requires_grad or any(s.requires_grad for s in srcs) or
                 any(p.requires_grad for p in params))
-            if need_grad:
+            if need_grad and 0 < self.checkpoint_planes < dv.shape[1]:
+                cost = _SweepTrainCkpt.apply(self, sweep, self.checkpoint_planes, ref_proj, src_projs, dv,
+                                             ref, *srcs, *params)
+            elif need_grad:   # (one segment is the whole record)
                 cost = _SweepTrain.apply(self, sweep, ref_proj, src_projs, dv, ref, *srcs, *params)
             else:
                 cost = sweep(ref, srcs, ref_proj, src_projs, dv, want_depth=False,

@@ -153,7 +153,49 @@ typedef struct aarmvs_sweep_args {
   const aarmvs_train_record* record;      /* training record, or NULL (eval): the cost
                                              slices and regulariser tensors of the planes
                                              d_begin..d_end-1 go to its slabs           */
+  int record_d0;                          /* segment record (see below): the first plane the
+                                             record holds; 0: the record starts at plane 0 */
+  int record_planes;                      /* planes the record holds; 0: up to plane D      */
 } aarmvs_sweep_args;
+
+/* Segment records (plane-segment checkpointing of the BPTT).
+ * A record may hold only the planes record_d0 .. record_d0 + n - 1 (n = record_planes, or
+ * D - record_d0 when that is 0): slab i of x, z, u, stats, t1 and ostats is then plane
+ * record_d0 + i, state slab i the state BEFORE plane record_d0 + i, and the record has n + 1
+ * state slabs.  aarmvs_train_segment_bytes gives its size.  A recorded aarmvs_sweep over
+ * [d_begin, d_end) inside that range reads its initial state from state slab d_begin -
+ * record_d0 (the library zeroes it only when d_begin == 0) and writes the other slabs at their
+ * segment-relative places; cost_out stays indexed by the absolute plane.  Such a call does not
+ * depend on what an earlier call left in the workspace (it re-makes the feature copies and the
+ * fp16 guard bound), except for depth_out / conf_out, whose winner-take-all images are only
+ * complete after contiguous calls from plane 0 through one workspace.
+ *
+ * Training with one S-plane record (S a multiple of 16) instead of a D-plane one:
+ *   forward, for each segment [s0, s1) = [0,S), [S,2S), ... in order:
+ *     aarmvs_sweep(d_begin = s0, d_end = s1, record_d0 = s0, record_planes = s1 - s0); copy
+ *     state slab s1 - s0 out as the checkpoint "state before plane s1", and (unless this was
+ *     the last segment) also into state slab 0 for the next segment;
+ *   backward, for each segment LAST FIRST, with one `scratch` that nothing else writes between
+ *   the calls:
+ *     copy the checkpoint "state before plane s0" into state slab 0 and repeat the segment's
+ *     recorded aarmvs_sweep (not needed while the record still holds the segment), then
+ *     aarmvs_sweep_backward(d_begin = s0, d_end = s1, record_d0 = s0, record_planes = s1 - s0).
+ * The backward's 16-plane groups are then the whole backward's, everything it carries from one
+ * group to the next (the cells' state gradients, the fp64 parameter accumulators and the
+ * cost-slice accumulators) lives in `scratch`, and every reduction has a fixed order: the
+ * gradients equal the whole-record backward's bit for bit.
+ *
+ * The new fields are appended to the existing structs rather than given entry points of their
+ * own: a zero-initialised struct keeps its meaning (whole D, record from plane 0), every
+ * caller of the old form compiles and behaves as before, and the sweep keeps ONE validated
+ * path instead of two that must be kept equal.  The structs carry no size field, so a caller
+ * compiled against the shorter structs has to be recompiled with this header; the library and
+ * its bindings (aarmvs/_lib.py) are built from one tree. */
+int aarmvs_train_segment_bytes(int B, int H, int W, int nsrc, int planes, size_t* record_bytes,
+                               size_t* checkpoint_bytes);
+/* ^ bytes of a record of `planes` planes (all seven buffers: planes slabs of x, z, u and stats,
+ * planes + 1 of state, planes * nsrc of t1 and ostats) and of one checkpoint (one state slab,
+ * 264 B per pixel at B = 1); either pointer may be NULL. */
 
 size_t aarmvs_sweep_workspace_bytes(int B, int H, int W, int nsrc);
 int aarmvs_sweep(const aarmvs_sweep_args* args, hipStream_t stream);
@@ -195,6 +237,19 @@ typedef struct aarmvs_backward_args {
   void* workspace;
   void* scratch;
   int regulariser_only;
+  /* Ranged backward (all zero: the whole backward over [0, D) on a whole record).  The call
+   * runs the planes [d_begin, d_end) (d_end == 0 means D) on a record that holds the planes
+   * record_d0 .. (see "Segment records" above).  d_begin and d_end must be multiples of 16,
+   * except that d_end may equal D.  The calls of one backward come last range first
+   * (d_end == D), each range ending where the one before began, down to d_begin == 0, with the
+   * same `scratch`, which nothing may write between the calls (the recompute aarmvs_sweep does
+   * not take it; the `workspace` may serve that sweep).  The call with d_end == D zeroes the
+   * carried state gradients and accumulators; the call with d_begin == 0 writes grad_params,
+   * grad_ref and grad_src (the other calls leave them untouched and may pass NULL for them).
+   * grad_x and grad_cost stay indexed by the absolute plane.  The library keeps no state of its
+   * own between the calls, so their order is the caller's contract and is not checked. */
+  int d_begin, d_end;
+  int record_d0, record_planes;
 } aarmvs_backward_args;
 size_t aarmvs_backward_scratch_bytes(int B, int H, int W, int nsrc);
 int aarmvs_sweep_backward(const aarmvs_backward_args* args, hipStream_t stream);
