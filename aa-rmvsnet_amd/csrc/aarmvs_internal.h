@@ -103,6 +103,10 @@ struct Workspace {
   float* u1;              // [B,16,H,W]     deconv_1 output (pre-GN)
   float* h[5][kHRingMax]; // hidden states: a ring of kHRing[k] slots (plane d reads slot d % r
                           // and writes slot (d + 1) % r)
+  float* h_pool[2][kHRingMax]; // maxpool2x2 of h[0] / h[1]'s slots (a quarter their size): part of
+                          // the slot -- same index, written by the same unit, waited on by the
+                          // same event; past the zero-initialised state region (cells 1 and 2
+                          // read only what cells 0 and 1 of the same plane wrote)
   float* c[5];            // cell states (updated in place)
   size_t bytes;
   size_t omega_stats_bytes;  // one plane
@@ -174,6 +178,8 @@ hipError_t launch_cost_x_group(const CostArgs& a, const SweepGeom& g, const Work
 struct UnetIO {
   const float* h_prev[5];
   float* h_new[5];
+  float* h_pool[2];     // maxpool2x2(h_new[0 / 1]) [B][Hk/2][Wk/2][16], written by cells 0 and 1 for
+                        // cells 1 and 2, or null (training record: the consumers pool h_new)
   const float* c_prev[5];
   float* c_new[5];
   float* z[5];          // gate pre-activations [B][Hk][Wk][4 hid], or null (eval)

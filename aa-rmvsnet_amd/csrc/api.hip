@@ -198,6 +198,10 @@ Workspace carve_workspace(void* base, int B, int H, int W, int nsrc) {
     ws.c[k] = reinterpret_cast<float*>(take(n));
   }
   ws.state_bytes = off - state_begin;
+  for (int k = 0; k < 2; ++k)
+    for (int r = 0; r < kHRingMax; ++r)
+      ws.h_pool[k][r] = r < kHRing[k] ? reinterpret_cast<float*>(take((size_t)B * kCellHid[k] * (cell_px[k] / 4) * 4))
+                                      : nullptr;
   ws.bytes = off;
   return ws;
 }

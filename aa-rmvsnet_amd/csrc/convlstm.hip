@@ -87,6 +87,7 @@ struct CellArgs {
   ChanSrc part[3];
   int nparts;
   float* h_new;
+  float* h_pool;        // CellDef::POOL_OUT: maxpool2x2(h') out, [B][H/2][W/2][HID]
   float* c;             // c' out ([B][H][W][HID]); the eval sweep updates c in place (c_in == c)
   const float* c_in;    // c of the previous plane
   float* z_out;         // training record: the gate pre-activations (conv + bias), or null: planar,
@@ -156,6 +157,9 @@ struct CellDef<0> {   // [x, h0] @ H
   static constexpr int H3RW = 1, H3WAVES = 8, H3DB = 1, H3PIPE = 1, H3MS = 1;
   static constexpr int MIN_WAVES = 1;   // amdgpu_waves_per_eu lower bound (register budget)
   static constexpr int SKEW = 3;        // CellArgs::skew of the double-buffered kernel
+  static constexpr bool XPART = true;   // part 0 is the cost slice x (staged at the xbound scale)
+  static constexpr int PATCH_ROWS = 1;  // pixel rows of a wave's 32-pixel n-tile (h3_tile_row)
+  static constexpr bool POOL_OUT = false;   // the epilogue also stores maxpool2x2(h')
 };
 template <>
 struct CellDef<1> {   // [maxpool(h0'), h1] @ H/2
@@ -165,6 +169,9 @@ struct CellDef<1> {   // [maxpool(h0'), h1] @ H/2
   static constexpr int H3RW = 1, H3WAVES = 8, H3DB = 1, H3PIPE = 1, H3MS = 1;
   static constexpr int MIN_WAVES = 1;
   static constexpr int SKEW = 2;
+  static constexpr bool XPART = false;
+  static constexpr int PATCH_ROWS = 1;
+  static constexpr bool POOL_OUT = false;
 };
 template <>
 struct CellDef<2> : CellDef<1> {};   // [maxpool(h1'), h2] @ H/4
@@ -176,6 +183,9 @@ struct CellDef<3> {   // [gnrelu(u0), h1', h3] @ H/2
   static constexpr int H3RW = 1, H3WAVES = 8, H3DB = AARMVS_C3DB, H3PIPE = 1, H3MS = 1;
   static constexpr int MIN_WAVES = 1;
   static constexpr int SKEW = AARMVS_C3SKEW;
+  static constexpr bool XPART = false;
+  static constexpr int PATCH_ROWS = 1;
+  static constexpr bool POOL_OUT = false;
 };
 template <>
 struct CellDef<4> {   // [gnrelu(u1), h0', h4] @ H
@@ -187,6 +197,35 @@ struct CellDef<4> {   // [gnrelu(u1), h0', h4] @ H
   // compiler's choice to 130, one block per CU: 160 -> 202 us per plane at the headline)
   static constexpr int MIN_WAVES = 4;
   static constexpr int SKEW = AARMVS_C4SKEW;
+  static constexpr bool XPART = false;
+  static constexpr int PATCH_ROWS = 1;
+  static constexpr bool POOL_OUT = false;
+};
+// The inference sweep's cells 0-2 with the pooled hidden state handed down in memory: cells 0
+// and 1 store maxpool2x2(h') from their accumulator registers beside h' (POOL_OUT), cells 1 and
+// 2 stage that quarter-size image as a plain part instead of pooling the fine one themselves
+// (SRC_POOL: four loads per haloed pixel, the halo fetched again by the neighbouring tile).
+// PATCH_ROWS = 2: a wave's n-tile is a 2-row x 16-column patch of the block tile instead of one
+// 32-pixel row, so every 2x2 window lies within one wave and the pooled value needs two lane
+// exchanges and no LDS or barrier (cell_epilogue).  Kinds 5-7 are never training cells.
+template <>
+struct CellDef<5> : CellDef<0> {   // cell 0, stores pool(h0')
+  static constexpr int PATCH_ROWS = 2;
+  static constexpr bool POOL_OUT = true;
+};
+template <>
+struct CellDef<6> : CellDef<1> {   // cell 1: [pool(h0') as stored by cell 0, h1], stores pool(h1')
+  static constexpr int MODE[kMaxParts] = {SRC_PLAIN, SRC_PLAIN, SRC_PLAIN};
+  static constexpr int PATCH_ROWS = 2;
+  static constexpr bool POOL_OUT = true;
+};
+template <>
+struct CellDef<7> : CellDef<1> {   // cell 2: [pool(h1') as stored by cell 1, h2]
+  static constexpr int MODE[kMaxParts] = {SRC_PLAIN, SRC_PLAIN, SRC_PLAIN};
+};
+template <>
+struct CellDef<8> : CellDef<0> {   // (tools/microbench/cell_bench only: cell 0's patch without the store)
+  static constexpr int PATCH_ROWS = 2;
 };
 
 // ---------------------------------------------------------------------------
@@ -221,6 +260,10 @@ struct H3Cfg {
   static constexpr int HID = D::HID, MT = HID / 8, COUT = 4 * HID;
   static constexpr int RW = RW_, WAVES = WAVES_, MS = MS_, MTL = MT / MS, RWAVES = WAVES / MS;
   static_assert(MT % MS == 0 && WAVES % MS == 0, "whole m-tiles and rows per wave");
+  static constexpr int PATCH = D::PATCH_ROWS;
+  static constexpr bool POOL_OUT = D::POOL_OUT;
+  static_assert(PATCH == 1 || (PATCH == 2 && RW == 1 && RWAVES % 2 == 0), "2 x 16 patches pair the row groups");
+  static_assert(!POOL_OUT || PATCH == 2, "the pooled store needs the 2x2 window within a wave");
   static constexpr int TH = RW * RWAVES, THREADS = WAVES * 64, TW = 32, W2 = TW + 2, TROWS = TH + 2;
   static constexpr int NPIX = TROWS * W2;
   static constexpr int A_HALVES = NCHK * 9 * MT * 64 * 8;   // per hi / lo
@@ -236,6 +279,27 @@ struct H3Cfg {
   // 8 valid channels: two taps per k-step (h3_mfma_chunk), the chunk's second half unused
   static constexpr bool chunk_paired(int c) { return chunk_nv(c) == 8; }
 };
+
+// Pixel of the block tile (row, column; the haloed image's pixel is one down and right) that
+// MFMA column n = lane & 31 of row group g holds.  PATCH 1: row g RW (.. + RW - 1), column n.
+// PATCH 2: the row groups are RWAVES / 2 row pairs x 2 column halves and the n-tile is the
+// 2 x 16 patch: row 2 (g >> 1) + (n >> 4), column 16 (g & 1) + ((n - 2 (n >> 4)) & 15) -- the
+// patch's second row rotated by two lanes.  Banks: under h3_pix's half swap a ds_read_b128 lane
+// group is conflict-free when its 16 haloed pixel indices differ mod 16.  The hardware's groups
+// are not runs of 16 lanes but {0-3, 12-15, 20-27} and {4-11, 16-19, 28-31} (and the same + 32):
+// on a 32-pixel row each covers all 16 residues; on an unrotated 2 x 16 patch the second row
+// (+W2 = 34 = 2 mod 16) would put lanes 20-27 on residues 6-13 against 0-3 and 12-15 of lanes
+// 0-3 and 12-15, a 2-way conflict on every B fragment read (measured: cell 0 +5%); rotated, lanes
+// 20-27 hold columns 2-9 (residues 4-11) and lanes 16-19, 28-31 columns 14, 15, 0, 1, 10-13
+// (residues 0-3, 12-15).  The rotation is even, so lane ^ 1 is still the x neighbour.
+template <class C>
+__device__ __forceinline__ int h3_tile_row(int g, int n) {
+  return C::PATCH == 2 ? 2 * (g >> 1) + (n >> 4) : g * C::RW;
+}
+template <class C>
+__device__ __forceinline__ int h3_tile_col(int g, int n) {
+  return C::PATCH == 2 ? 16 * (g & 1) + ((n - 2 * (n >> 4)) & 15) : n;
+}
 
 // byte offset of (pixel p, 16-B half h) in a chunk plane
 __device__ __forceinline__ int h3_pix(int p, int h) { return p * 32 + ((h ^ ((p >> 3) & 1)) << 4); }
@@ -266,7 +330,9 @@ struct H3PixStager {
   static constexpr int NITEM = 2 * C::NPIX;
   static constexpr int NI = (NITEM + TH - 1) / TH;
   static_assert(NI <= 32, "item mask holds 32 items");
-  float val[NI][8][4];   // [item][channel][POOL window: fine (2y,2x) (2y,2x+1) (2y+1,2x) (2y+1,2x+1)]
+  static constexpr int NWMAX =
+      (D::MODE[0] == SRC_POOL || D::MODE[1] == SRC_POOL || D::MODE[2] == SRC_POOL) ? 4 : 1;
+  float val[NI][8][NWMAX];   // [item][channel][POOL window: fine (2y,2x) (2y,2x+1) (2y+1,2x) (2y+1,2x+1)]
   uint32_t in_mask;      // bit j: item j is an in-image pixel of valid channels
   float xs = 1.0f;       // 2^-e staging scale of part 0: cell 0's x (xguard_exp), cells 3 and
                          // 4's GroupNorm+ReLU part (gguard_exp); h parts: 2^kHScaleExp
@@ -333,7 +399,7 @@ struct H3PixStager {
           } else if (MODE == SRC_GNRELU) {
             const int lc = LC0 + 8 * h + k;
             x = fmaxf(val[j][k][0] * gn[lc] + gn[16 + lc], 0.0f) * xs;
-          } else if constexpr (KIND == 0 && C::chunk_part(CH) == 0) {
+          } else if constexpr (D::XPART && C::chunk_part(CH) == 0) {
             x = val[j][k][0] * xs;
           } else {
             x = val[j][k][0] * HS;
@@ -357,7 +423,7 @@ struct H3PixStager {
 template <class C, int KIND, int CH, bool BAL>
 __device__ __forceinline__ void xguard_rescale(floatx16 (&acc)[C::MTL][C::RW], floatx16 (&accn)[C::MTL][C::RW],
                                                float xr) {
-  if constexpr ((KIND == 0 || C::D::MODE[0] == SRC_GNRELU) && CH > 0 && C::chunk_part(CH) != 0 &&
+  if constexpr ((C::D::XPART || C::D::MODE[0] == SRC_GNRELU) && CH > 0 && C::chunk_part(CH) != 0 &&
                 C::chunk_part(CH - 1) == 0) {
 #pragma unroll
     for (int m = 0; m < C::MTL; ++m)
@@ -393,7 +459,9 @@ __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], fl
                                               const char* in_lo, int wave, int lane, int m0 = 0) {
   // wave: the wave's row group (its rows wave RW ..); m0: its first m-tile (H3Cfg::MS)
   constexpr int MT = C::MT, MTL = C::MTL, RW = C::RW;
-  const int col = lane & 31, h = lane >> 5;
+  const int h = lane >> 5;
+  // the lane's pixel of the haloed tile at tap 0, row 0 (h3_tile_row / h3_tile_col)
+  const int p0 = h3_tile_row<C>(wave, lane & 31) * C::W2 + h3_tile_col<C>(wave, lane & 31);
   if constexpr (C::chunk_paired(CH)) {
     // (PIPE ignored: the plain fragment schedule.)  The lane's tap offsets are recomputed here
     // rather than hoisted out of the tile loop (5 live VGPRs: the training cell spilled)
@@ -405,7 +473,7 @@ __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], fl
       half8 bh[RW], bl[RW];
 #pragma unroll
       for (int r = 0; r < RW; ++r) {
-        const int boff = h3_pix((wave * RW + r + tap / 3) * C::W2 + col + tap % 3, 0);
+        const int boff = h3_pix(p0 + (r + tap / 3) * C::W2 + tap % 3, 0);
         bh[r] = *reinterpret_cast<const half8*>(in_hi + boff);
         bl[r] = *reinterpret_cast<const half8*>(in_lo + boff);
       }
@@ -432,7 +500,7 @@ __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], fl
       } else
 #pragma unroll
       for (int r = 0; r < RW; ++r) {
-        const int boff = h3_pix((wave * RW + r + tap / 3) * C::W2 + col + tap % 3, h);
+        const int boff = h3_pix(p0 + (r + tap / 3) * C::W2 + tap % 3, h);
         bh[s][r] = *reinterpret_cast<const half8*>(in_hi + boff);
         bl[s][r] = *reinterpret_cast<const half8*>(in_lo + boff);
       }
@@ -471,7 +539,7 @@ __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], fl
       half8 bh[RW], bl[RW];
 #pragma unroll
       for (int r = 0; r < RW; ++r) {
-        const int p = (wave * RW + r + tap / 3) * C::W2 + col + tap % 3;
+        const int p = p0 + (r + tap / 3) * C::W2 + tap % 3;
         const int boff = h3_pix(p, h);
         bh[r] = *reinterpret_cast<const half8*>(in_hi + boff);
         bl[r] = *reinterpret_cast<const half8*>(in_lo + boff);
@@ -520,6 +588,7 @@ __device__ __forceinline__ void cell_epilogue(const CellArgs& a, const floatx16 
                                               const float (&cst)[C::MTL][C::RW][4], float inv_scale,
                                               int b, int yw, int x, int hi, int m0 = 0) {
   constexpr int HID = C::HID;
+  float hp[C::MTL][4] = {};   // POOL_OUT (RW = 1): this lane's h'
 #pragma unroll
   for (int r = 0; r < C::RW; ++r) {
     const int y = yw + r;
@@ -550,6 +619,9 @@ __device__ __forceinline__ void cell_epilogue(const CellArgs& a, const floatx16 
         const size_t o = pix * HID + m * 8 + 4 * hi;
         *reinterpret_cast<float4*>(a.c + o) = make_float4(cn[0], cn[1], cn[2], cn[3]);
         *reinterpret_cast<float4*>(a.h_new + o) = make_float4(hn[0], hn[1], hn[2], hn[3]);
+        if constexpr (C::POOL_OUT)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) hp[ml][q] = hn[q];
         if (a.z_out) {   // gates i, f, o, g of channels m*8 + 4 hi .. +3 (module.py:83)
           // planar record layout [B][HID/4 channel quads][4 gates][H*W][4]: a wave's stores of
           // one gate are contiguous (512 B per half-wave)
@@ -567,6 +639,35 @@ __device__ __forceinline__ void cell_epilogue(const CellArgs& a, const floatx16 
           }
         }
       }
+    }
+  }
+  if constexpr (C::POOL_OUT) {
+    // maxpool2x2(h') from registers.  In a 2 x 16 patch the window's x partner is lane ^ 1 (a
+    // DPP quad permute) and its y partner the second-row lane of the same column, lane
+    // 16 + ((n + 2) & 15) (h3_tile_col: ds_bpermute, which moves registers through the LDS
+    // crossbar but touches no LDS memory), both in this wave.  The lane of the window's pixel
+    // (0, 0) forms fmaxf(fmaxf(v00, v01), fmaxf(v10, v11)), the operand order of the SRC_POOL
+    // staging, and stores it.  Every lane takes part in the exchanges (they are outside the
+    // bounds branch); the image sizes are even (H and W are multiples of 4 at cell 0), so a
+    // window is wholly inside the image or wholly outside.  (A VALU-only exchange, a row rotate
+    // by DPP and v_permlane16_swap, measured the same: what the pooled output costs cell 0 is the
+    // store, not the exchange -- profiles/pooled_h_ab.txt.)
+    static_assert(!PRECISE && C::RW == 1, "inference cells only");
+    const bool owner = !(yw & 1) && !(x & 1) && yw < a.H && x < a.W;
+    const int Hp = a.H >> 1, Wp = a.W >> 1;
+    const int lane = threadIdx.x & 63, below = (lane & 32) | 16 | ((lane + 2) & 15);
+#pragma unroll
+    for (int ml = 0; ml < C::MTL; ++ml) {
+      float pm[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float vx = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(hp[ml][q]), 0xB1, 0xF, 0xF, true));
+        const float rowmax = fmaxf(hp[ml][q], vx);
+        pm[q] = fmaxf(rowmax, __shfl(rowmax, below));
+      }
+      if (owner)
+        *reinterpret_cast<float4*>(a.h_pool + (((size_t)b * Hp + (yw >> 1)) * Wp + (x >> 1)) * HID +
+                                   (m0 + ml) * 8 + 4 * hi) = make_float4(pm[0], pm[1], pm[2], pm[3]);
     }
   }
 }
@@ -614,7 +715,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
   // the inference cells skip a paired chunk's unused half; the training cells (PRECISE) keep
   // the uniform staging loop (skipping it costs the 128-VGPR cell 4 spills there)
   H3PixStager<KIND, RW, WAVES, 0, !PRECISE, MS> st;
-  const int xe = KIND == 0 ? xguard_exp(a.xbound)
+  const int xe = D::XPART ? xguard_exp(a.xbound)
                  : D::MODE[0] == SRC_GNRELU ? gguard_exp(a.part[0].gamma, a.part[0].beta, H, W) : 0;
   st.xs = ldexpf(1.0f, -xe);
   const float xr = ldexpf(1.0f, xe + kHScaleExp);   // part 0's units -> the h parts' 2^kHScaleExp
@@ -632,7 +733,8 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
     const int next = tile + (int)gridDim.x;
     int nb = 0, ny0 = 0, nx0 = 0;
     if (next < ntiles) coords(next, nb, ny0, nx0);
-    const int yw = y0 + rwave * RW;   // this wave's first row
+    const int yw = y0 + h3_tile_row<C>(rwave, col);   // this lane's (first) row and its column
+    const int x = x0 + h3_tile_col<C>(rwave, col);
     floatx16 acc[MT][RW], accn[MT][RW];   // sign-balanced pair (h3_mfma_chunk)
 #pragma unroll
     for (int m = 0; m < MT; ++m)
@@ -653,7 +755,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
       } else if (next < ntiles) {
         st.template load<0>(a, nb, ny0, nx0, tid);
       }
-      if (CH == 0) cell_c_load<C>(a, b, yw, x0 + col, hi, cst, m0);
+      if (CH == 0) cell_c_load<C>(a, b, yw, x, hi, cst, m0);
       xguard_rescale<C, KIND, CH, PRECISE>(acc, accn, xr);
       if (!(ABL & 1)) h3_mfma_chunk<C, CH, PIPE != 0, PRECISE, (ABL >> 3) & 3>(acc, accn, wl_hi, wl_lo, in_hi, in_lo, rwave, lane, m0);
     };
@@ -665,7 +767,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
 #pragma unroll
       for (int r = 0; r < RW; ++r)
         if constexpr (PRECISE) acc[m][r] -= accn[m][r];
-    cell_epilogue<C, ABL, PRECISE>(a, acc, cst, inv_scale, b, yw, x0 + col, hi, m0);
+    cell_epilogue<C, ABL, PRECISE>(a, acc, cst, inv_scale, b, yw, x, hi, m0);
   }
 }
 
@@ -714,7 +816,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
   int tile = blockIdx.x;
   if (tile >= ntiles) return;   // whole block
   H3PixStager<KIND, RW, WAVES, 0, false, MS> st;
-  const int xe = KIND == 0 ? xguard_exp(a.xbound)
+  const int xe = D::XPART ? xguard_exp(a.xbound)
                  : D::MODE[0] == SRC_GNRELU ? gguard_exp(a.part[0].gamma, a.part[0].beta, H, W) : 0;
   st.xs = ldexpf(1.0f, -xe);
   const float xr = ldexpf(1.0f, xe + kHScaleExp);   // part 0's units -> the h parts' 2^kHScaleExp
@@ -736,8 +838,8 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
     const int next = tile + (int)gridDim.x;
     int nb = 0, ny0 = 0, nx0 = 0;
     if (next < ntiles) coords(next, nb, ny0, nx0);
-    const int yw = y0 + rwave * RW;   // this wave's first row
-    const int x = x0 + col;
+    const int yw = y0 + h3_tile_row<C>(rwave, col);   // this lane's (first) row and its column
+    const int x = x0 + h3_tile_col<C>(rwave, col);
     floatx16 acc[MT][RW], accn[MT][RW];   // sign-balanced pair (h3_mfma_chunk)
     float cst[MT][RW][4];
 #pragma unroll
@@ -838,8 +940,13 @@ template <int KIND, int RW = CellDef<KIND>::H3RW, int WAVES = CellDef<KIND>::H3W
           int DB = CellDef<KIND>::H3DB, int PIPE = CellDef<KIND>::H3PIPE, int MS = CellDef<KIND>::H3MS>
 static hipError_t run_cell_h3(const CellArgs& a, const float* inv_scale, int cu, int kid,
                               hipStream_t s) {
-  return a.z_out ? run_cell_h3_<KIND, RW, WAVES, ABL, DB, PIPE, true, MS>(a, inv_scale, cu, kid, s)
-                 : run_cell_h3_<KIND, RW, WAVES, ABL, DB, PIPE, false, MS>(a, inv_scale, cu, kid, s);
+  if constexpr (KIND >= 5) {   // the pooled-h kinds: inference only (launch_unet_step)
+    return a.z_out ? hipErrorInvalidValue
+                   : run_cell_h3_<KIND, RW, WAVES, ABL, DB, PIPE, false, MS>(a, inv_scale, cu, kid, s);
+  } else {
+    return a.z_out ? run_cell_h3_<KIND, RW, WAVES, ABL, DB, PIPE, true, MS>(a, inv_scale, cu, kid, s)
+                   : run_cell_h3_<KIND, RW, WAVES, ABL, DB, PIPE, false, MS>(a, inv_scale, cu, kid, s);
+  }
 }
 
 // Tile shape of the cells with two or more m-tiles (round 6, second session; every shape is
@@ -1366,6 +1473,7 @@ UnetIO unet_io_ws(const Workspace& ws, int d) {
     io.c_new[k] = ws.c[k];
     io.z[k] = nullptr;
   }
+  for (int k = 0; k < 2; ++k) io.h_pool[k] = ws.h_pool[k][h_slot(k, d + 1)];
   io.u0 = ws.u0;
   io.u1 = ws.u1;
   io.reg_stats = ws.reg_stats;
@@ -1424,24 +1532,41 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
     a.c_in += b * hid * px;
     if (a.z_out) a.z_out += b * 4 * hid * px;
   };
+  // The inference sweep hands maxpool2x2(h0') and maxpool2x2(h1') down in memory (CellDef<5..7>:
+  // cells 0 and 1 store them from registers, cells 1 and 2 stage them as plain parts); the
+  // training sweep, whose record has no pooled images, and AARMVS_CELL_POOL=0 keep the cells
+  // that pool the fine image while staging it.  Bit-identical either way.
+  static const bool pool_env = [] {
+    const char* v = std::getenv("AARMVS_CELL_POOL");   // read once: the units of one plane agree
+    return !(v && *v) || std::atoi(v) != 0;
+  }();
+  const bool pooled = pool_env && io.h_pool[0] && io.h_pool[1] && !io.z[0] && !io.z[1] && !io.z[2];
   if (stages & 1) {
   // cell 0: [x, h0] @ H
   CellArgs a0 = cell(0, {{x, 32, SRC_PLAIN, nullptr, nullptr, nullptr},
                          {io.h_prev[0], 16, SRC_PLAIN, nullptr, nullptr, nullptr}}, 1);
   a0.xbound = ws.xbound;
-  if ((e = run_cell<0>(a0, params + L.h3_scale_off + 0, cu, K_CELL0, s)) != hipSuccess) return e;
+  a0.h_pool = pooled ? io.h_pool[0] : nullptr;
+  e = pooled ? run_cell<5>(a0, params + L.h3_scale_off + 0, cu, K_CELL0, s)
+             : run_cell<0>(a0, params + L.h3_scale_off + 0, cu, K_CELL0, s);
+  if (e != hipSuccess) return e;
   }
   if (stages & 2) {
   // cell 1: [maxpool(h0'), h1] @ H/2
-  CellArgs a1 = cell(1, {{io.h_new[0], 16, SRC_POOL, nullptr, nullptr, nullptr},
+  CellArgs a1 = cell(1, {{pooled ? io.h_pool[0] : io.h_new[0], 16, pooled ? SRC_PLAIN : SRC_POOL, nullptr, nullptr, nullptr},
                          {io.h_prev[1], 16, SRC_PLAIN, nullptr, nullptr, nullptr}}, 2);
-  if ((e = run_cell<1>(a1, params + L.h3_scale_off + 1, cu, K_CELL1, s)) != hipSuccess) return e;
+  a1.h_pool = pooled ? io.h_pool[1] : nullptr;
+  e = pooled ? run_cell<6>(a1, params + L.h3_scale_off + 1, cu, K_CELL1, s)
+             : run_cell<1>(a1, params + L.h3_scale_off + 1, cu, K_CELL1, s);
+  if (e != hipSuccess) return e;
   }
   if (stages & 4) {
   // cell 2: [maxpool(h1'), h2] @ H/4
-  CellArgs a2 = cell(2, {{io.h_new[1], 16, SRC_POOL, nullptr, nullptr, nullptr},
+  CellArgs a2 = cell(2, {{pooled ? io.h_pool[1] : io.h_new[1], 16, pooled ? SRC_PLAIN : SRC_POOL, nullptr, nullptr, nullptr},
                          {io.h_prev[2], 16, SRC_PLAIN, nullptr, nullptr, nullptr}}, 4);
-  if ((e = run_cell<2>(a2, params + L.h3_scale_off + 2, cu, K_CELL2, s)) != hipSuccess) return e;
+  e = pooled ? run_cell<7>(a2, params + L.h3_scale_off + 2, cu, K_CELL2, s)
+             : run_cell<2>(a2, params + L.h3_scale_off + 2, cu, K_CELL2, s);
+  if (e != hipSuccess) return e;
   }
   // GroupNorm statistics are per batch element, so the two cells that consume the deconvs'
   // normalised outputs are launched per batch element; each reduces its element's deconv

@@ -260,7 +260,10 @@ int aarmvs_sweep_backward(const aarmvs_backward_args* args, hipStream_t stream);
  * ring indexed by planes % kHRing[k]: 6, 4, 3, 3 and 2 slots for h0..h4, so that the units of
  * neighbouring planes can run on separate streams.  The rings are part of
  * aarmvs_sweep_workspace_bytes: 572 B per pixel against 264 B for two slots each; at
- * 1600x1184 and B = 1, h0 alone takes about 485 MB more).  Valid after an
+ * 1600x1184 and B = 1, h0 alone takes about 485 MB more.  Each slot of the h0 and h1 rings
+ * also has a quarter-size image of the 2x2 max-pooled h, written by the inference sweep's
+ * cells 0 and 1 for cells 1 and 2: 112 B per pixel more, 212 MB at 1600x1184 and B = 1;
+ * aarmvs_state_ptr does not expose them).  Valid after an
  * aarmvs_sweep call; returns a device pointer to [B,H_k,W_k,hid_k] (NHWC: the workspace
  * keeps the U-Net tensors channel-innermost) or NULL. */
 float* aarmvs_state_ptr(void* workspace, int B, int H, int W, int nsrc, int planes,

@@ -77,6 +77,68 @@ int main() {
   const double fl0 = 2.0 * 9 * 48 * 64 * HW, fl1 = 2.0 * 9 * 32 * 64 * HW / 4, fl3 = 2.0 * 9 * 48 * 64 * HW / 4,
                fl4 = 2.0 * 9 * 40 * 32 * HW;
   auto h3 = [&](CellArgs a) { a.wpk = reinterpret_cast<const float*>(wh); return a; };
+  if (getenv("CB_POOL") && atoi(getenv("CB_POOL"))) {
+    // Pooled h from the producer (CellDef<5..7>): cells 1 and 2 with part 0 plain on a quarter-size
+    // image against the library's SRC_POOL staging, and what the 2 x 16 patch and the pooled
+    // store cost cells 0 and 1.  Cell 2 runs cell 1's kernel at H/4.
+    float* pool = rnd_buf(16 * HW / 4, 1.f);
+    auto pl = [&](CellArgs a, bool plain_in) {
+      if (plain_in) a.part[0].mode = SRC_PLAIN;
+      a.h_pool = pool;
+      return h3(a);
+    };
+    {   // h, c of kinds 5-7 against kinds 0-2, and the pooled images against a host max-pool
+      std::vector<float> c0(16 * HW), h1(16 * HW), h2(16 * HW), c1(16 * HW), c2(16 * HW), pg(16 * HW / 4);
+      CK(hipMemcpy(c0.data(), cst, 16 * HW * 4, hipMemcpyDeviceToHost));
+      auto once = [&](auto fn, std::vector<float>& ho, std::vector<float>& co) {
+        CK(hipMemcpy(cst, c0.data(), 16 * HW * 4, hipMemcpyHostToDevice));
+        CK(fn()); CK(hipDeviceSynchronize());
+        CK(hipMemcpy(ho.data(), hout, 16 * HW * 4, hipMemcpyDeviceToHost));
+        CK(hipMemcpy(co.data(), cst, 16 * HW * 4, hipMemcpyDeviceToHost));
+      };
+      auto pool_ok = [&](int Hc, int Wc) {   // pool == maxpool2x2(h1), same operand order
+        CK(hipMemcpy(pg.data(), pool, (size_t)16 * (Hc / 2) * (Wc / 2) * 4, hipMemcpyDeviceToHost));
+        for (int y = 0; y < Hc / 2; ++y)
+          for (int x = 0; x < Wc / 2; ++x)
+            for (int c = 0; c < 16; ++c) {
+              auto at = [&](int yy, int xx) { return h1[((size_t)yy * Wc + xx) * 16 + c]; };
+              const float r = fmaxf(fmaxf(at(2 * y, 2 * x), at(2 * y, 2 * x + 1)), fmaxf(at(2 * y + 1, 2 * x), at(2 * y + 1, 2 * x + 1)));
+              if (memcmp(&r, &pg[((size_t)y * (Wc / 2) + x) * 16 + c], 4)) return false;
+            }
+        return true;
+      };
+      once([&] { return run_cell_h3<0, 1, 8, 0, 1, 1>(h3(args(0, 1)), invs, 256, K_CELL0, 0); }, h2, c2);
+      once([&] { return run_cell_h3<5, 1, 8, 0, 1, 1>(pl(args(0, 1), false), invs, 256, K_CELL0, 0); }, h1, c1);
+      printf("  cell0 2x16 + pooled store vs library: %s, pooled image %s\n",
+             !memcmp(h1.data(), h2.data(), 16 * HW * 4) && !memcmp(c1.data(), c2.data(), 16 * HW * 4) ? "bit-identical" : "DIFFERENT",
+             pool_ok(H, W) ? "exact" : "WRONG");
+      // cell 1 from cell 0's pooled image (f16a is what the library form pools)
+      CK(hipMemcpy(f16a, hout, 16 * HW * 4, hipMemcpyDeviceToDevice));
+      float* p0 = rnd_buf(16 * HW / 4, 0.f);
+      CK(hipMemcpy(p0, pool, 16 * HW / 4 * 4, hipMemcpyDeviceToDevice));
+      auto from_p0 = [&](CellArgs a) { a.part[0].ptr = p0; return a; };
+      once([&] { return run_cell_h3<1, 1, 8, 0, 1, 1>(h3(args(1, 2)), invs, 256, K_CELL1, 0); }, h2, c2);
+      once([&] { return run_cell_h3<6, 1, 8, 0, 1, 1>(from_p0(pl(args(1, 2), true)), invs, 256, K_CELL1, 0); }, h1, c1);
+      printf("  cell1 plain pooled input, 2x16 + pooled store vs library: %s, pooled image %s\n",
+             !memcmp(h1.data(), h2.data(), 16 * HW / 4 * 4) && !memcmp(c1.data(), c2.data(), 16 * HW / 4 * 4) ? "bit-identical" : "DIFFERENT",
+             pool_ok(H / 2, W / 2) ? "exact" : "WRONG");
+      once([&] { return run_cell_h3<7, 1, 8, 0, 1, 1>(from_p0(pl(args(1, 2), true)), invs, 256, K_CELL1, 0); }, h1, c1);
+      printf("  cell1 plain pooled input vs library: %s\n",
+             !memcmp(h1.data(), h2.data(), 16 * HW / 4 * 4) && !memcmp(c1.data(), c2.data(), 16 * HW / 4 * 4) ? "bit-identical" : "DIFFERENT");
+      CK(hipMemcpy(cst, c0.data(), 16 * HW * 4, hipMemcpyHostToDevice));
+    }
+    for (int rep = 0; rep < 2; ++rep) {
+      run("cell0 library", [&] { return run_cell_h3<0, 1, 8, 0, 1, 1>(h3(args(0, 1)), invs, 256, K_CELL0, 0); }, fl0);
+      run("cell0 2x16, no pooled store (8)", [&] { return run_cell_h3<8, 1, 8, 0, 1, 1>(h3(args(0, 1)), invs, 256, K_CELL0, 0); }, fl0);
+      run("cell0 2x16 + pooled store (5)",[&] { return run_cell_h3<5, 1, 8, 0, 1, 1>(pl(args(0, 1), false), invs, 256, K_CELL0, 0); }, fl0);
+      run("cell1 library (SRC_POOL)", [&] { return run_cell_h3<1, 1, 8, 0, 1, 1>(h3(args(1, 2)), invs, 256, K_CELL1, 0); }, fl1);
+      run("cell1 plain pooled input (7)", [&] { return run_cell_h3<7, 1, 8, 0, 1, 1>(pl(args(1, 2), true), invs, 256, K_CELL1, 0); }, fl1);
+      run("cell1 plain in, 2x16 + store (6)", [&] { return run_cell_h3<6, 1, 8, 0, 1, 1>(pl(args(1, 2), true), invs, 256, K_CELL1, 0); }, fl1);
+      run("cell2 library (SRC_POOL)", [&] { return run_cell_h3<1, 1, 8, 0, 1, 1>(h3(args(1, 4)), invs, 256, K_CELL2, 0); }, fl1 / 4);
+      run("cell2 plain pooled input (7)", [&] { return run_cell_h3<7, 1, 8, 0, 1, 1>(pl(args(1, 4), true), invs, 256, K_CELL2, 0); }, fl1 / 4);
+    }
+    return 0;
+  }
   if (small) {
     {   // MS=2 against the library config: h and c bit-identical (fresh c for each)
       std::vector<float> c0(16 * HW), h1(16 * HW), h2(16 * HW), c1(16 * HW), c2(16 * HW);

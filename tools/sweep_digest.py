@@ -1,4 +1,4 @@
-"""Digest of an eval sweep's outputs at 640x512, N=3, PROBE_D planes (default 48): run under
+"""Digest of an eval sweep's outputs at PROBE_W x PROBE_H (default 640x512), N=3, PROBE_D planes (default 48): run under
 different environment switches (AARMVS_OMEGA_IPB, AARMVS_NPL, ...) to confirm a schedule
 change is bit-identical."""
 import hashlib
@@ -11,7 +11,8 @@ import torch  # noqa: E402
 
 from aarmvs import ops, synthetic as syn  # noqa: E402
 
-B, N, H, W, D = 1, 3, 512, 640, int(os.environ.get("PROBE_D", "48"))
+B, N, D = 1, 3, int(os.environ.get("PROBE_D", "48"))
+H, W = int(os.environ.get("PROBE_H", "512")), int(os.environ.get("PROBE_W", "640"))   # config 1: 128, 160
 sc = syn.scene(B, N, H, W, D, seed=0)
 P = {k: torch.from_numpy(v).cuda() for k, v in syn.sweep_weights(1).items()}
 sw = ops.DepthSweep(P, "cuda")
