@@ -40,12 +40,18 @@ typedef float bfloatx4 __attribute__((ext_vector_type(4)));
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ float acc_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
-// power-of-two exponent e with max * 2^-e in [2^14, 2^15) (0 for an all-zero tensor)
+// power-of-two exponent e with max * 2^-e in [2^14, 2^15) (0 for an all-zero tensor).  Below
+// 2^-100 the exponent stays at -114, as the forward's guard_exp_of (convlstm.hip) holds it:
+// every consumer forms 2^-e = ldexpf(1.0f, -e), which is +inf from e = -128 (max < 2^-113) on,
+// and inf * 0 or the lo part inf - inf of a staged value would turn a plane group whose
+// gradient has all but vanished into NaN.  Such a group's values stay finite (<= 2^15) and are
+// staged less accurately, relative to a gradient that is itself below 2^-100.
 __device__ __forceinline__ int scale_exp(unsigned bits) {
   const float m = __uint_as_float(bits);
   if (!(m > 0.0f)) return 0;
   if (!(m < INFINITY)) return 120;
-  return ilogbf(m) - 14;
+  const int k = ilogbf(m);
+  return k < -100 ? -114 : k - 14;
 }
 
 // a pair (a, b) split the same way: the hi pair as one v_cvt_pk_f16_f32 read back for the lo

@@ -144,6 +144,10 @@ __global__ void __launch_bounds__(256) warp_bwd_max_kernel(const float* __restri
     atomicMax(gmax + b, (unsigned)w);
 }
 
+// bound on |k| of the fixed-point exponents (warp_bwd_exp, cbw_scale_kernel): 2^k is applied
+// with ldexp on values whose scaled magnitude is <= 2^61, and removed in fp64
+constexpr int kFixedExpMax = 250;
+
 // the fixed-point exponent of a batch element; false: its grad_out is not finite
 __device__ __forceinline__ bool warp_bwd_exp(unsigned maxbits, int HW, int& k) {
   const float mx = __uint_as_float(maxbits);
@@ -151,8 +155,11 @@ __device__ __forceinline__ bool warp_bwd_exp(unsigned maxbits, int HW, int& k) {
   if (!(mx <= FLT_MAX)) return false;
   const double tot = (double)mx * (double)HW;
   if (!(tot > 0.0)) return true;
+  // (the clamp is wider than any finite fp32 grad_out needs, |kk| <= ~230 down to subnormal
+  // maxima: a tighter one, +-120 until the range tests, left a gradient of 2^-96 only ~40 of
+  // the sum's 61 bits below its bound and cost dL/dsrc 5e-5 of its norm)
   const int kk = 61 - ilogb(tot) - 1;
-  k = kk > 120 ? 120 : (kk < -120 ? -120 : kk);
+  k = kk > kFixedExpMax ? kFixedExpMax : (kk < -kFixedExpMax ? -kFixedExpMax : kk);
   return true;
 }
 
@@ -1786,8 +1793,8 @@ __global__ void cbw_scale_kernel(const unsigned* __restrict__ gmax, const unsign
     const double tot = g * (double)HW * (double)n;
     int k = 0;
     if (tot > 0.0 && tot < 1e300) {
-      k = 61 - ilogb(tot) - 1;
-      k = k > 120 ? 120 : (k < -120 ? -120 : k);
+      k = 61 - ilogb(tot) - 1;   // never clamped for finite fp32 maxima (warp_bwd_exp)
+      k = k > kFixedExpMax ? kFixedExpMax : (k < -kFixedExpMax ? -kFixedExpMax : k);
     }
     *fxk = k;
   }

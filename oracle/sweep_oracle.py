@@ -155,6 +155,9 @@ def omega_weight(sq: torch.Tensor, P: dict, fast: bool = False) -> torch.Tensor:
 
 # test hook: called with every omega logit tensor (the input of the final sigmoid) if set
 LOGIT_HOOK = None
+# test hook: called with every ConvLSTM cell's conv output [B, 4 hid, h, w] if set; unet_step
+# calls the cells in the order 0..4, so call number n is cell n % 5 of plane n // 5
+GATE_HOOK = None
 
 
 def cost_slice(ref_fea, src_feas, rels, depth, P, fast: bool = False) -> torch.Tensor:
@@ -176,6 +179,8 @@ CELL_HID = (16, 16, 16, 16, 8)
 
 def lstm_cell(x, h, c, w, b):
     z = F.conv2d(torch.cat([x, h], 1), w, b, padding=1)
+    if GATE_HOOK is not None:   # tests: the gate pre-activations (their gradients are dL/dz)
+        GATE_HOOK(z)
     i, f, o, g = torch.split(z, h.shape[1], dim=1)
     c2 = torch.sigmoid(f) * c + torch.sigmoid(i) * torch.tanh(g)
     h2 = torch.sigmoid(o) * torch.tanh(c2)

@@ -167,18 +167,18 @@ def bound(name, e_cpu32):
     return max(2e-5, 2.0 * e_cpu32)
 
 
-def _f32_spread(feats, proj, dv, P, R, g64):
+def _f32_spread(feats, proj, dv, P, R, g64, loss="softmax"):
     """{tensor: max over F32_THREADS of float32 autograd's relative L2 error vs float64};
     keys 'features', 'x', the parameter names and, per (view, batch element) slice of the
     feature gradient, 'features[v,b]' (an error confined to one view's slice is small in the
-    whole tensor's norm).  g64 = _oracle_grads(..., float64)."""
+    whole tensor's norm).  g64 = _oracle_grads(..., float64, loss)."""
     _, gf64, gp64, gx64 = g64
     prev = torch.get_num_threads()
     worst = {}
     try:
         for n in F32_THREADS:
             torch.set_num_threads(n)
-            _, gf32, gp32, gx32 = _oracle_grads(feats, proj, dv, P, R, torch.float32)
+            _, gf32, gp32, gx32 = _oracle_grads(feats, proj, dv, P, R, torch.float32, loss)
             e = {"features": rel_l2(gf32.numpy(), gf64.numpy()),
                  "x": rel_l2(np.stack([g.numpy() for g in gx32]), np.stack([g.numpy() for g in gx64]))}
             for k in gp64:
@@ -193,9 +193,14 @@ def _f32_spread(feats, proj, dv, P, R, g64):
     return worst
 
 
-def _oracle_grads(feats, proj, dv, P, R, dtype):
+def _oracle_grads(feats, proj, dv, P, R, dtype, loss="softmax", keep=None):
     """float64/float32 autograd of the oracle's sweep (the reference's arithmetic) ->
-    (prob, d/dfeatures, {param: grad}, [dL/dx_d])."""
+    (prob, d/dfeatures, {param: grad}, [dL/dx_d]).  loss "softmax": L = sum(R * softmax(cost))
+    over D; "linear": L = sum(R * cost) over the stacked raw costs, so that dL/dcost = R exactly
+    (any cotangent in closed form; conv_0.bias's gradient is sum(R)).  keep: a dict that
+    receives the raw cost volume [B,D,H,W] as keep["cost"]."""
+    if loss not in ("softmax", "linear"):
+        raise ValueError(loss)
     from oracle import sweep_oracle as orc
     N, B, C, H, W = feats.shape
     fc = feats.to(dtype).clone().requires_grad_(True)
@@ -209,8 +214,11 @@ def _oracle_grads(feats, proj, dv, P, R, dtype):
         xs.append(x)
         cost, state = orc.unet_step(x, state, Pp)
         costs.append(cost)
-    prob = torch.softmax(torch.stack(costs, 1).squeeze(2), dim=1)
-    (prob * R.to(dtype)).sum().backward()
+    vol = torch.stack(costs, 1).squeeze(2)
+    prob = torch.softmax(vol, dim=1)
+    ((prob if loss == "softmax" else vol) * R.to(dtype)).sum().backward()
+    if keep is not None:
+        keep["cost"] = vol.detach()
     return prob.detach(), fc.grad, {k: v.grad for k, v in Pp.items()}, [x.grad for x in xs]
 
 
