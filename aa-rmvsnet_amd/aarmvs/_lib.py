@@ -120,6 +120,7 @@ SIGNATURES = {
                                           c_void_p, c_void_p, c_void_p]),
     "aarmvs_sweep_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "aarmvs_sweep": (c_int, [ctypes.POINTER(SweepArgs), c_void_p]),
+    "aarmvs_sweep_p": (c_int, [ctypes.POINTER(SweepArgs), c_int, c_void_p]),
     "aarmvs_aux_stream": (c_int, [ctypes.POINTER(c_void_p)]),
     "aarmvs_train_record_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "aarmvs_train_segment_bytes": (c_int, [c_int] * 5 + [ctypes.POINTER(c_size_t)] * 2),
@@ -128,6 +129,8 @@ SIGNATURES = {
     "aarmvs_state_ptr": (c_void_p, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "aarmvs_unet_step": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p]),
+    "aarmvs_unet_step_p": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_int, c_void_p]),
     "aarmvs_softmax_depth": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "aarmvs_lstm_gates_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                           c_void_p]),

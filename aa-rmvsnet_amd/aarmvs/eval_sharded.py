@@ -53,6 +53,8 @@ def parse_args(argv=None):
     ap.add_argument("--interval_scale", type=float, default=1.0)
     ap.add_argument("--loadckpt", default=None)
     ap.add_argument("--outdir", default="./outputs")
+    # not in eval.py: the regulariser's precision mode (aarmvs.ops.DepthSweep)
+    ap.add_argument("--sweep_precision", choices=("split", "fp16"), default="split")
     return ap.parse_args(argv)
 
 
@@ -92,7 +94,8 @@ def save_depth(args, rank: int = 0, world: int = 1, device=None, model=None) -> 
                         drop_last=False)
     if model is None:
         model = EMVSNet(disparity_level=32, image_scale=args.image_scale, max_h=args.max_h,
-                        max_w=args.max_w, return_depth=True)
+                        max_w=args.max_w, return_depth=True,
+                        sweep_precision=getattr(args, "sweep_precision", "split"))
         if args.loadckpt:
             load_checkpoint(model, args.loadckpt)
     model = model.to(device).eval()

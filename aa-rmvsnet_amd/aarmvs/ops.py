@@ -493,17 +493,35 @@ class DepthSweep:
     Holds the packed parameters and a workspace per (B, H, W, nsrc) geometry.
     """
 
-    def __init__(self, params: dict, device, overlap: bool = True):
-        """``overlap``: run the next plane group's cost stage on a second stream (the library's
+    PRECISIONS = {"split": 0, "fp16": 1}  # aarmvs_precision (include/aarmvs.h)
+
+    def __init__(self, params: dict, device, overlap: bool = True, precision: str = "split"):
+        """``precision``: ``"split"`` (the default, the parity mode: three fp16 matrix products
+        per fp32 product of the regulariser's convs) or ``"fp16"`` (opt-in, inference only: one
+        product, the conv operands rounded once to fp16; DESIGN.md §7).  Settable afterwards;
+        ``__call__`` and ``unet_step`` use the current value.
+
+        ``overlap``: run the next plane group's cost stage on a second stream (the library's
         aux stream, aux_stream()) beside the current group's regulariser steps, and spread each
         plane's U-Net step over the library's streams so that the steps of neighbouring planes
         overlap (four streams in all; small frames move the cost stage to the current stream;
         same results, bit for bit)."""
+        self.precision = precision  # (validated before anything touches the device)
         self.device = torch.device(device)
         self.packed = pack_params(params, self.device)
         self._ws = {}
         self._aux = None
         self.overlap = overlap
+
+    @property
+    def precision(self) -> str:
+        return self._precision
+
+    @precision.setter
+    def precision(self, mode: str):
+        if mode not in self.PRECISIONS:
+            raise AarmvsError(f"aarmvs: precision must be one of {sorted(self.PRECISIONS)}, got {mode!r}")
+        self._precision = mode
 
     @property
     def overlap(self) -> bool:
@@ -698,10 +716,13 @@ class DepthSweep:
         a.aux_stream = self._aux.cuda_stream if self._aux is not None else None
         rec_struct = None
         if record is not None:
+            if self._precision != "split":
+                raise AarmvsError(f"aarmvs: precision {self._precision!r} is an inference mode; a recorded "
+                                  "(training) sweep needs precision 'split'")
             rec_struct = self._segment_struct(a, record, record_d0, d0, d1, ref.device)
         elif record_d0:
             raise AarmvsError("aarmvs: record_d0 without a record")
-        check(lib().aarmvs_sweep(ctypes.byref(a), _stream()), "sweep")
+        check(lib().aarmvs_sweep_p(ctypes.byref(a), self.PRECISIONS[self._precision], _stream()), "sweep")
         out["_keepalive"] = (rel, dv, srcs, ref, rec_struct)
         return out
 
@@ -852,8 +873,9 @@ class DepthSweep:
         B, C, H, W = x.shape
         ws = self.workspace(B, H, W, nsrc)
         cost = torch.empty(B, 1, H, W, device=x.device)
-        check(lib().aarmvs_unet_step(x.data_ptr(), B, H, W, nsrc, step, self.packed.data_ptr(),
-                                     ws.data_ptr(), cost.data_ptr(), _stream()), "unet_step")
+        check(lib().aarmvs_unet_step_p(x.data_ptr(), B, H, W, nsrc, step, self.packed.data_ptr(),
+                                       ws.data_ptr(), cost.data_ptr(), self.PRECISIONS[self._precision],
+                                       _stream()), "unet_step")
         return cost
 
 

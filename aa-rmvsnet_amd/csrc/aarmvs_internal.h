@@ -207,11 +207,13 @@ UnetIO unet_io_record(const TrainLayout& T, const aarmvs_train_record& r, int d)
 // stages: the step's five units (bit u = unit u, run in that order: cell 0 | cell 1 | cell 2 |
 // deconv_0 + cell 3 | deconv_1 + cell 4); a unit of plane d reads only the earlier units'
 // outputs of plane d and its own state, so the units of neighbouring planes may run at once on
-// different streams (the sweep's multi-stream regulariser)
+// different streams (the sweep's multi-stream regulariser).  precision: aarmvs_precision -- the
+// split cells and deconvs (three fp16 products per fp32 product) or, for inference steps only
+// (no io.z), their 1-product fp16 variants
 constexpr int kUnetAll = (1 << kUnetUnits) - 1;
 hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom& g,
                             const Workspace& ws, const UnetIO& io, hipStream_t s,
-                            int stages = kUnetAll);
+                            int stages = kUnetAll, int precision = AARMVS_PREC_SPLIT);
 hipError_t launch_head_wta(const float* params, const SweepGeom& g, const UnetIO& io,
                            const Workspace& ws, const float* depth_values, int d,
                            float* cost_out, bool wta, hipStream_t s);
@@ -380,6 +382,9 @@ enum KernelId : int {
   K_DECONV_WGRAD, K_HEAD_WGRAD, K_DEFORM,
   K_PYR_DOWN, K_FUSION_POINTS,
   K_CLS_LOSS_FWD, K_CLS_LOSS_REDUCE, K_CLS_LOSS_BWD, K_DEPTH_METRICS,
+  // the fp16 mode's 1-product cells and deconvs (AARMVS_PREC_FP16), in the order of K_CELL0 ..
+  K_CELL0_FP16, K_CELL1_FP16, K_CELL2_FP16, K_CELL3_FP16, K_CELL4_FP16,
+  K_DECONV0_FP16, K_DECONV1_FP16,
   K_COUNT
 };
 extern bool g_prof_on;

@@ -99,7 +99,9 @@ static const char* kKernelNames[K_COUNT] = {
     "gnb_partial", "deconv_bwd", "bwd_small", "cbw_chain", "cbw_feat", "cbw_small",
     "deconv_wgrad", "head_wgrad", "deform_sample",
     "pyr_down", "fusion_points",
-    "cls_loss_fwd", "cls_loss_reduce", "cls_loss_bwd", "depth_metrics"};
+    "cls_loss_fwd", "cls_loss_reduce", "cls_loss_bwd", "depth_metrics",
+    "lstm_cell0_fp16", "lstm_cell1_fp16", "lstm_cell2_fp16", "lstm_cell3_fp16", "lstm_cell4_fp16",
+    "deconv0_fp16", "deconv1_fp16"};
 
 static hipEvent_t prof_event() {
   if (g_prof_used == g_prof_pool.size()) {
@@ -679,6 +681,7 @@ struct HipSweep {
   const CostArgs& ca;
   hipEvent_t* ev;
   hipStream_t st[kSweepSlots];
+  int precision = AARMVS_PREC_SPLIT;   // aarmvs_precision of the regulariser's units
   int rc = 0, io_d = -1;
   UnetIO io_{};
 
@@ -740,12 +743,13 @@ struct HipSweep {
   }
   int step(const SweepGroup& grp, int d) {
     const UnetIO& all = io(d, false);
-    if (int r = check(launch_unet_step(slice(grp, d), ca.params, g, ws, all, st[0]), "sweep: regulariser step"))
+    if (int r = check(launch_unet_step(slice(grp, d), ca.params, g, ws, all, st[0], kUnetAll, precision),
+                      "sweep: regulariser step"))
       return r;
     return head_on(st[0], all, d);
   }
   int unit(int slot, int u, const SweepGroup& grp, int d) {
-    return check(launch_unet_step(slice(grp, d), ca.params, g, ws, io(d, true), st[slot], 1 << u),
+    return check(launch_unet_step(slice(grp, d), ca.params, g, ws, io(d, true), st[slot], 1 << u, precision),
                  "sweep: regulariser step");
   }
   int head(int slot, int d) { return head_on(st[slot], io(d, true), d); }
@@ -760,7 +764,18 @@ struct HipSweep {
 extern "C" {
 
 int aarmvs_sweep(const aarmvs_sweep_args* a, hipStream_t stream) {
+  return aarmvs_sweep_p(a, AARMVS_PREC_SPLIT, stream);
+}
+
+int aarmvs_sweep_p(const aarmvs_sweep_args* a, int precision, hipStream_t stream) {
   if (!a) return fail(AARMVS_ERR_INVALID, "sweep: null args");
+  if (precision != AARMVS_PREC_SPLIT && precision != AARMVS_PREC_FP16)
+    return fail(AARMVS_ERR_INVALID, "sweep: unknown precision " + std::to_string(precision) +
+                                        " (AARMVS_PREC_SPLIT = 0, AARMVS_PREC_FP16 = 1)");
+  if (precision == AARMVS_PREC_FP16 && a->record)
+    return fail(AARMVS_ERR_INVALID,
+                "sweep: AARMVS_PREC_FP16 is an inference mode; a training record needs AARMVS_PREC_SPLIT "
+                "(the backward differentiates the split cells)");
   int rc = check_geom(a->B, a->H, a->W, a->nsrc);
   if (rc) return rc;
   if (a->C != kC) return fail(AARMVS_ERR_INVALID, "sweep: feature channels C must be 32");
@@ -819,6 +834,7 @@ int aarmvs_sweep(const aarmvs_sweep_args* a, hipStream_t stream) {
     evs.dev = dev;
   }
   HipSweep run{a, T, g, ws, ca, evs.ev, {}};
+  run.precision = precision;
   for (int i = 0; i < kSweepSlots; ++i) {
     const SweepStream id = plan.slot[i];
     if (id == kCaller) run.st[i] = stream;
@@ -1000,6 +1016,15 @@ int aarmvs_wta_update(const float* cost, const float* depth_d, float* max_prob, 
 int aarmvs_unet_step(const float* x, int B, int H, int W, int nsrc, int step,
                      const void* packed_params, void* workspace, float* cost_out,
                      hipStream_t stream) {
+  return aarmvs_unet_step_p(x, B, H, W, nsrc, step, packed_params, workspace, cost_out, AARMVS_PREC_SPLIT, stream);
+}
+
+int aarmvs_unet_step_p(const float* x, int B, int H, int W, int nsrc, int step,
+                       const void* packed_params, void* workspace, float* cost_out, int precision,
+                       hipStream_t stream) {
+  if (precision != AARMVS_PREC_SPLIT && precision != AARMVS_PREC_FP16)
+    return fail(AARMVS_ERR_INVALID, "unet_step: unknown precision " + std::to_string(precision) +
+                                        " (AARMVS_PREC_SPLIT = 0, AARMVS_PREC_FP16 = 1)");
   int rc = check_geom(B, H, W, nsrc);
   if (rc) return rc;
   if (!x || !packed_params || !workspace || !cost_out || step < 0)
@@ -1019,7 +1044,7 @@ int aarmvs_unet_step(const float* x, int B, int H, int W, int nsrc, int step,
   if ((e = launch_layout(x, ws.x, B, kC, H * W, true, stream, ws.xbound)) != hipSuccess)
     return hip_fail(e, "unet_step: x layout");
   const UnetIO io = unet_io_ws(ws, step);
-  if ((e = launch_unet_step(ws.x, params, g, ws, io, stream)) != hipSuccess)
+  if ((e = launch_unet_step(ws.x, params, g, ws, io, stream, kUnetAll, precision)) != hipSuccess)
     return hip_fail(e, "unet_step");
   // head conv only (no WTA): cost_out is [B,1,H,W] == [B,D=1,H,W] at plane 0
   if ((e = launch_head_wta(params, g, io, ws, nullptr, 0, cost_out, false, stream)) !=

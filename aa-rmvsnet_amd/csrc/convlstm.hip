@@ -252,13 +252,17 @@ typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 // MS: waves per tile row -- each of a row's MS waves takes MT / MS of the m-tiles (the gates of
 // 8 hidden channels per m-tile: the LSTM update of those channels is the wave's own), so a block
 // of WAVES waves covers WAVES / MS rows
-template <int KIND, int RW_ = CellDef<KIND>::H3RW, int WAVES_ = CellDef<KIND>::H3WAVES, int MS_ = 1>
+// PROD: products per k-step -- 3: the split form above; 1: the opt-in fp16 mode (w_hi x_hi only:
+// every operand rounded once to fp16 at its staging scale, no lo planes in LDS)
+template <int KIND, int RW_ = CellDef<KIND>::H3RW, int WAVES_ = CellDef<KIND>::H3WAVES, int MS_ = 1, int PROD_ = 3>
 struct H3Cfg {
   using D = CellDef<KIND>;
   static constexpr int CIN = D::CH[0] + D::CH[1] + D::CH[2];
   static constexpr int NCHK = (CIN + 15) / 16;
   static constexpr int HID = D::HID, MT = HID / 8, COUT = 4 * HID;
   static constexpr int RW = RW_, WAVES = WAVES_, MS = MS_, MTL = MT / MS, RWAVES = WAVES / MS;
+  static constexpr int PROD = PROD_, PLANES = PROD == 3 ? 2 : 1;   // LDS planes per operand: hi (, lo)
+  static_assert(PROD == 3 || PROD == 1, "three split products or one");
   static_assert(MT % MS == 0 && WAVES % MS == 0, "whole m-tiles and rows per wave");
   static constexpr int PATCH = D::PATCH_ROWS;
   static constexpr bool POOL_OUT = D::POOL_OUT;
@@ -267,7 +271,7 @@ struct H3Cfg {
   static constexpr int TH = RW * RWAVES, THREADS = WAVES * 64, TW = 32, W2 = TW + 2, TROWS = TH + 2;
   static constexpr int NPIX = TROWS * W2;
   static constexpr int A_HALVES = NCHK * 9 * MT * 64 * 8;   // per hi / lo
-  static constexpr size_t LDS_BYTES = (size_t)A_HALVES * 2 * 2 + (size_t)NPIX * 32 * 2 + 32 * 4;
+  static constexpr size_t LDS_BYTES = (size_t)A_HALVES * 2 * PLANES + (size_t)NPIX * 32 * PLANES + 32 * 4;
   static constexpr int c0(int p) { return p == 0 ? 0 : (p == 1 ? D::CH[0] : D::CH[0] + D::CH[1]); }
   static constexpr int chunk_part(int c) {
     return 16 * c < c0(1) ? 0 : (16 * c < c0(2) || D::NP < 3 ? 1 : 2);
@@ -315,6 +319,11 @@ __device__ __forceinline__ uint32_t h3_split2(float a, float b, uint32_t& lo_bit
   return __builtin_bit_cast(uint32_t, hi);
 }
 
+// (a, b) -> one fp16 pair (round to nearest even): the 1-product form's only conversion
+__device__ __forceinline__ uint32_t h3_pack2(float a, float b) {
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector((float2_t){a, b}, half2_t));
+}
+
 // Input staging: item = (half h of the chunk's 16 channels, pixel p of the haloed tile),
 // consecutive lanes on consecutive pixels.  The U-Net tensors are NHWC ([B][H][W][C]), so
 // an item's 8 channels are 32 contiguous bytes (two 16-B loads; POOL: two per fine pixel
@@ -322,9 +331,9 @@ __device__ __forceinline__ uint32_t h3_split2(float a, float b, uint32_t& lo_bit
 // each LDS plane as ONE 16-B store (8 channels as fp16 pairs) at h3_pix(p, h): 2-way bank
 // conflicts at most.  Out-of-image pixels and channels past the chunk's valid count load
 // zeros through the buffer range check.  NTH: staging threads (default: the block).
-template <int KIND, int RW, int WAVES, int NTH = 0, bool PAIRSKIP = false, int MS = 1>
+template <int KIND, int RW, int WAVES, int NTH = 0, bool PAIRSKIP = false, int MS = 1, int PROD = 3>
 struct H3PixStager {
-  using C = H3Cfg<KIND, RW, WAVES, MS>;
+  using C = H3Cfg<KIND, RW, WAVES, MS, PROD>;
   using D = typename C::D;
   static constexpr int TH = NTH ? NTH : C::THREADS;   // staging threads
   static constexpr int NITEM = 2 * C::NPIX;
@@ -406,12 +415,19 @@ struct H3PixStager {
           }
           v[k] = in ? x : 0.0f;
         }
-        uint32_t hw[4], lw[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) hw[i] = h3_split2(v[2 * i], v[2 * i + 1], lw[i]);
         const int off = h3_pix(p, h);
-        *reinterpret_cast<u32x4*>(hi_plane + off) = u32x4{hw[0], hw[1], hw[2], hw[3]};
-        *reinterpret_cast<u32x4*>(lo_plane + off) = u32x4{lw[0], lw[1], lw[2], lw[3]};
+        if constexpr (PROD == 3) {
+          uint32_t hw[4], lw[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) hw[i] = h3_split2(v[2 * i], v[2 * i + 1], lw[i]);
+          *reinterpret_cast<u32x4*>(hi_plane + off) = u32x4{hw[0], hw[1], hw[2], hw[3]};
+          *reinterpret_cast<u32x4*>(lo_plane + off) = u32x4{lw[0], lw[1], lw[2], lw[3]};
+        } else {   // one conversion per value, no lo plane (lo_plane is not a buffer)
+          uint32_t hw[4];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) hw[i] = h3_pack2(v[2 * i], v[2 * i + 1]);
+          *reinterpret_cast<u32x4*>(hi_plane + off) = u32x4{hw[0], hw[1], hw[2], hw[3]};
+        }
       }
     }
   }
@@ -453,12 +469,17 @@ __device__ __forceinline__ void xguard_rescale(floatx16 (&acc)[C::MTL][C::RW], f
 // K half of lanes 0-31 and tap 2s+1 in the K half of lanes 32-63 (the weights packed to match,
 // pack_cell_h3_kernel), so the chunk costs 5 k-steps instead of 9 with a zero K half each;
 // tap 9 of step 4 is a zero weight against tap 8's pixels.
+//
+// C::PROD == 1 (the fp16 mode): only the hi fragments are read and each product is one MFMA;
+// wl_lo and in_lo are not buffers then.
 template <class C, int CH, bool PIPE = false, bool BAL = true, int ONCE = 0>
 __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], floatx16 (&accn)[C::MTL][C::RW],
                                               const char* wl_hi, const char* wl_lo, const char* in_hi,
                                               const char* in_lo, int wave, int lane, int m0 = 0) {
   // wave: the wave's row group (its rows wave RW ..); m0: its first m-tile (H3Cfg::MS)
   constexpr int MT = C::MT, MTL = C::MTL, RW = C::RW;
+  constexpr bool SPLIT = C::PROD == 3;
+  static_assert(SPLIT || (!BAL && !ONCE), "the 1-product form: inference cells only");
   const int h = lane >> 5;
   // the lane's pixel of the haloed tile at tap 0, row 0 (h3_tile_row / h3_tile_col)
   const int p0 = h3_tile_row<C>(wave, lane & 31) * C::W2 + h3_tile_col<C>(wave, lane & 31);
@@ -475,19 +496,22 @@ __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], fl
       for (int r = 0; r < RW; ++r) {
         const int boff = h3_pix(p0 + (r + tap / 3) * C::W2 + tap % 3, 0);
         bh[r] = *reinterpret_cast<const half8*>(in_hi + boff);
-        bl[r] = *reinterpret_cast<const half8*>(in_lo + boff);
+        if constexpr (SPLIT) bl[r] = *reinterpret_cast<const half8*>(in_lo + boff);
       }
 #pragma unroll
       for (int m = 0; m < MTL; ++m) {
         const int aoff = ((((CH * 9 + s) * MT + m0 + m) * 64) + lane) * 16;
         const half8 ah = *reinterpret_cast<const half8*>(wl_hi + aoff);
-        const half8 al = *reinterpret_cast<const half8*>(wl_lo + aoff);
+        half8 al;
+        if constexpr (SPLIT) al = *reinterpret_cast<const half8*>(wl_lo + aoff);
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
           floatx16& d = (BAL && ((s + CH) & 1)) ? accn[m][r] : acc[m][r];
           d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[r], d, 0, 0, 0);
-          d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[r], d, 0, 0, 0);
-          d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[r], d, 0, 0, 0);
+          if constexpr (SPLIT) {
+            d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[r], d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[r], d, 0, 0, 0);
+          }
         }
       }
     }
@@ -502,7 +526,7 @@ __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], fl
       for (int r = 0; r < RW; ++r) {
         const int boff = h3_pix(p0 + (r + tap / 3) * C::W2 + tap % 3, h);
         bh[s][r] = *reinterpret_cast<const half8*>(in_hi + boff);
-        bl[s][r] = *reinterpret_cast<const half8*>(in_lo + boff);
+        if constexpr (SPLIT) bl[s][r] = *reinterpret_cast<const half8*>(in_lo + boff);
       }
       if ((ONCE & 1) && tap > 0) {   // microbenchmark ablation: A fragments of tap 0 only
 #pragma unroll
@@ -513,7 +537,7 @@ __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], fl
       for (int m = 0; m < MTL; ++m) {
         const int aoff = ((((CH * 9 + tap) * MT + m0 + m) * 64) + lane) * 16;
         ah[s][m] = *reinterpret_cast<const half8*>(wl_hi + aoff);
-        al[s][m] = *reinterpret_cast<const half8*>(wl_lo + aoff);
+        if constexpr (SPLIT) al[s][m] = *reinterpret_cast<const half8*>(wl_lo + aoff);
       }
     };
     fetch(0, 0);
@@ -528,8 +552,10 @@ __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], fl
         for (int r = 0; r < RW; ++r) {
           floatx16& d = (BAL && ((tap + CH) & 1)) ? accn[m][r] : acc[m][r];
           d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s][m], bh[s][r], d, 0, 0, 0);
-          d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s][m], bl[s][r], d, 0, 0, 0);
-          d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s][m], bh[s][r], d, 0, 0, 0);
+          if constexpr (SPLIT) {
+            d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s][m], bl[s][r], d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[s][m], bh[s][r], d, 0, 0, 0);
+          }
         }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -542,19 +568,22 @@ __device__ __forceinline__ void h3_mfma_chunk(floatx16 (&acc)[C::MTL][C::RW], fl
         const int p = p0 + (r + tap / 3) * C::W2 + tap % 3;
         const int boff = h3_pix(p, h);
         bh[r] = *reinterpret_cast<const half8*>(in_hi + boff);
-        bl[r] = *reinterpret_cast<const half8*>(in_lo + boff);
+        if constexpr (SPLIT) bl[r] = *reinterpret_cast<const half8*>(in_lo + boff);
       }
 #pragma unroll
       for (int m = 0; m < MTL; ++m) {
         const int aoff = ((((CH * 9 + tap) * MT + m0 + m) * 64) + lane) * 16;
         const half8 ah = *reinterpret_cast<const half8*>(wl_hi + aoff);
-        const half8 al = *reinterpret_cast<const half8*>(wl_lo + aoff);
+        half8 al;
+        if constexpr (SPLIT) al = *reinterpret_cast<const half8*>(wl_lo + aoff);
 #pragma unroll
         for (int r = 0; r < RW; ++r) {
           floatx16& d = (BAL && ((tap + CH) & 1)) ? accn[m][r] : acc[m][r];
           d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[r], d, 0, 0, 0);
-          d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[r], d, 0, 0, 0);
-          d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[r], d, 0, 0, 0);
+          if constexpr (SPLIT) {
+            d = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[r], d, 0, 0, 0);
+            d = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[r], d, 0, 0, 0);
+          }
         }
       }
     }
@@ -676,27 +705,29 @@ __device__ __forceinline__ void cell_epilogue(const CellArgs& a, const floatx16 
 // ablation bits for the microbenchmark only (1 no MFMA, 2 no staging loads/stores, 4 no
 // gate math, 8 / 16 the A / B fragments read for tap 0 only)
 template <int KIND, int RW = CellDef<KIND>::H3RW, int WAVES = CellDef<KIND>::H3WAVES, int ABL = 0,
-          int PIPE = CellDef<KIND>::H3PIPE, bool PRECISE = false, int MS = 1>
+          int PIPE = CellDef<KIND>::H3PIPE, bool PRECISE = false, int MS = 1, int PROD = 3>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(CellDef<KIND>::MIN_WAVES))) lstm_cell_h3_kernel(
     CellArgs a, const float* __restrict__ inv_scale_ptr) {
-  using C = H3Cfg<KIND, RW, WAVES, MS>;
+  using C = H3Cfg<KIND, RW, WAVES, MS, PROD>;
   using D = typename C::D;
   constexpr int MT = C::MTL, NCHK = C::NCHK;
+  static_assert(PROD == 3 || !PRECISE, "the training cells are split cells");
+  // LDS: weight planes, input planes (hi then lo; PROD 1: hi only), the GroupNorm table
   extern __shared__ __attribute__((aligned(16))) char lds_h3[];
   char* wl_hi = lds_h3;
-  char* wl_lo = wl_hi + C::A_HALVES * 2;
-  char* in_hi = wl_lo + C::A_HALVES * 2;
-  char* in_lo = in_hi + C::NPIX * 32;
-  float* gn = reinterpret_cast<float*>(in_lo + C::NPIX * 32);
+  char* wl_lo = wl_hi + C::A_HALVES * 2;   // (PROD 1: not a buffer, never dereferenced)
+  char* in_hi = wl_hi + C::A_HALVES * 2 * C::PLANES;
+  char* in_lo = in_hi + C::NPIX * 32;      // (PROD 1: likewise)
+  float* gn = reinterpret_cast<float*>(in_hi + C::NPIX * 32 * C::PLANES);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int H = a.H, W = a.W;
   const float inv_scale = ldexpf(*inv_scale_ptr, -kHScaleExp);   // weight scale and staging scale
-  // split-fp16 weights -> LDS once per block
+  // split-fp16 weights -> LDS once per block (PROD 1: their hi planes, the first half)
   {
     const float4* s = reinterpret_cast<const float4*>(a.wpk);
     float4* d = reinterpret_cast<float4*>(wl_hi);
-    constexpr int N4 = C::A_HALVES * 2 * 2 / 16;
+    constexpr int N4 = C::A_HALVES * 2 * C::PLANES / 16;
 #pragma unroll 8
     for (int i = tid; i < N4; i += C::THREADS) d[i] = s[i];
   }
@@ -714,7 +745,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
   };
   // the inference cells skip a paired chunk's unused half; the training cells (PRECISE) keep
   // the uniform staging loop (skipping it costs the 128-VGPR cell 4 spills there)
-  H3PixStager<KIND, RW, WAVES, 0, !PRECISE, MS> st;
+  H3PixStager<KIND, RW, WAVES, 0, !PRECISE, MS, PROD> st;
   const int xe = D::XPART ? xguard_exp(a.xbound)
                  : D::MODE[0] == SRC_GNRELU ? gguard_exp(a.part[0].gamma, a.part[0].beta, H, W) : 0;
   st.xs = ldexpf(1.0f, -xe);
@@ -778,19 +809,21 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
 // the chunk after that; at a tile's last chunk, the gate epilogue.  Across the two
 // waves of a SIMD one wave's staging VALU work fills the other's MFMA issue gaps.
 template <int KIND, int RW = CellDef<KIND>::H3RW, int WAVES = CellDef<KIND>::H3WAVES, int ABL = 0,
-          int PIPE = CellDef<KIND>::H3PIPE, bool PRECISE = false, int MS = 1>
+          int PIPE = CellDef<KIND>::H3PIPE, bool PRECISE = false, int MS = 1, int PROD = 3>
 __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(CellDef<KIND>::MIN_WAVES))) lstm_cell_h3db_kernel(
     CellArgs a, const float* __restrict__ inv_scale_ptr) {
-  using C = H3Cfg<KIND, RW, WAVES, MS>;
+  using C = H3Cfg<KIND, RW, WAVES, MS, PROD>;
   using D = typename C::D;
   constexpr int MT = C::MTL, NCHK = C::NCHK;
   constexpr int PB = C::NPIX * 32;   // one plane (hi or lo) of one input buffer
+  constexpr int BB = C::PLANES * PB;  // one input buffer: hi plane (, lo plane)
   static_assert(NCHK >= 2, "two or more input chunks");
+  static_assert(PROD == 3 || !PRECISE, "the training cells are split cells");
   extern __shared__ __attribute__((aligned(16))) char lds_h3[];
   char* wl_hi = lds_h3;
-  char* wl_lo = wl_hi + C::A_HALVES * 2;
-  char* inb = wl_lo + C::A_HALVES * 2;   // buffer k: hi plane at 2k PB, lo plane at (2k+1) PB
-  float* gn = reinterpret_cast<float*>(inb + 4 * PB);
+  char* wl_lo = wl_hi + C::A_HALVES * 2;   // (PROD 1: not a buffer, never dereferenced)
+  char* inb = wl_hi + C::A_HALVES * 2 * C::PLANES;   // buffer k at k BB: hi plane, then (PROD 3) lo plane
+  float* gn = reinterpret_cast<float*>(inb + 2 * BB);
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int H = a.H, W = a.W;
@@ -798,7 +831,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
   {
     const float4* s = reinterpret_cast<const float4*>(a.wpk);
     float4* d = reinterpret_cast<float4*>(wl_hi);
-    constexpr int N4 = C::A_HALVES * 2 * 2 / 16;
+    constexpr int N4 = C::A_HALVES * 2 * C::PLANES / 16;
 #pragma unroll 8
     for (int i = tid; i < N4; i += C::THREADS) d[i] = s[i];
   }
@@ -815,7 +848,7 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
   };
   int tile = blockIdx.x;
   if (tile >= ntiles) return;   // whole block
-  H3PixStager<KIND, RW, WAVES, 0, false, MS> st;
+  H3PixStager<KIND, RW, WAVES, 0, false, MS, PROD> st;
   const int xe = D::XPART ? xguard_exp(a.xbound)
                  : D::MODE[0] == SRC_GNRELU ? gguard_exp(a.part[0].gamma, a.part[0].beta, H, W) : 0;
   st.xs = ldexpf(1.0f, -xe);
@@ -855,8 +888,8 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
       constexpr int F = F_NEXT ? 0 : CH + 1;
       constexpr bool A_NEXT = CH + 2 >= NCHK;   // the chunk after it
       constexpr int AC = A_NEXT ? CH + 2 - NCHK : CH + 2;
-      const char* cur = inb + 2 * par * PB;
-      char* oth = inb + 2 * (par ^ 1) * PB;
+      const char* cur = inb + par * BB;
+      char* oth = inb + (par ^ 1) * BB;
       auto stage = [&] {
         if (!(ABL & 2)) {
           if (!F_NEXT || next < ntiles) st.template store<F>(oth, oth + PB, gn, tid, 0, W);
@@ -904,18 +937,37 @@ __global__ void __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu
 // double-buffered too (95.0 -> 90.8 us per plane in the sweep), cell 4 still is not (161 -> 200).
 template <int KIND, int RW = CellDef<KIND>::H3RW, int WAVES = CellDef<KIND>::H3WAVES, int ABL = 0,
           int DB = CellDef<KIND>::H3DB, int PIPE = CellDef<KIND>::H3PIPE, bool PRECISE = false,
-          int MS = CellDef<KIND>::H3MS>
+          int MS = CellDef<KIND>::H3MS, int PROD = 3>
 static hipError_t run_cell_h3_(const CellArgs& a, const float* inv_scale, int cu, int kid,
                                hipStream_t s) {
-  using C = H3Cfg<KIND, RW, WAVES, MS>;
-  constexpr size_t lds = C::LDS_BYTES + (DB ? (size_t)C::NPIX * 32 * 2 : 0);
+  using C = H3Cfg<KIND, RW, WAVES, MS, PROD>;
+  constexpr size_t lds = C::LDS_BYTES + (DB ? (size_t)C::NPIX * 32 * C::PLANES : 0);
   static_assert(lds <= 160 * 1024, "h3 cell tile exceeds LDS");
-  const void* fn = DB ? (const void*)lstm_cell_h3db_kernel<KIND, RW, WAVES, ABL, PIPE, PRECISE, MS>
-                      : (const void*)lstm_cell_h3_kernel<KIND, RW, WAVES, ABL, PIPE, PRECISE, MS>;
+  // gn_table reduces in the input buffers (4 x 256 doubles), which the 1-product form halves
+  static_assert(CellDef<KIND>::MODE[0] != SRC_GNRELU || (size_t)C::NPIX * 32 * C::PLANES * (DB ? 2 : 1) >= 4 * 256 * 8,
+                "gn_table's scratch exceeds the launched kernel's input buffers");
+  const void* fn = DB ? (const void*)lstm_cell_h3db_kernel<KIND, RW, WAVES, ABL, PIPE, PRECISE, MS, PROD>
+                      : (const void*)lstm_cell_h3_kernel<KIND, RW, WAVES, ABL, PIPE, PRECISE, MS, PROD>;
   static bool attr_set[kMaxDevices] = {};
   if (hipError_t e = ensure_dyn_lds(fn, (int)lds, attr_set); e != hipSuccess) return e;
   const int ntiles = a.B * ((a.W + C::TW - 1) / C::TW) * ((a.H + C::TH - 1) / C::TH);
-  const int per_cu = std::max(1, (int)((160 * 1024) / lds));
+  int per_cu = std::max(1, (int)((160 * 1024) / lds));
+  if constexpr (PROD != 3) {
+    // The 1-product form's LDS (half the operand planes) admits more blocks per CU than its
+    // registers may: the persistent grid is sized by what is resident (asked once per device).
+    // Where both allow it the freed LDS doubles the blocks per CU with no change to a CellDef
+    // (cells 1 and 2 at <= 128 VGPRs); cells 0 and 3 keep one block (134-140 VGPRs).
+    static int occ[kMaxDevices] = {};
+    int dev = 0;
+    if (hipError_t e = current_device(dev); e != hipSuccess) return e;
+    if (!occ[dev]) {
+      int n = 0;
+      if (hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, C::THREADS, lds); e != hipSuccess)
+        return e;
+      occ[dev] = std::max(1, n);
+    }
+    per_cu = std::min(per_cu, occ[dev]);
+  }
   const int grid = std::max(1, std::min(ntiles, cu * per_cu));
   // the staging order of the double-buffered kernel's wave halves (lstm_cell_h3db_kernel): per
   // cell the wave bit measured fastest at the headline (tools/gpu_envsets_ab.sh over
@@ -927,22 +979,23 @@ static hipError_t run_cell_h3_(const CellArgs& a, const float* inv_scale, int cu
   ak.skew = skew_env >= 0 ? skew_env : CellDef<KIND>::SKEW;
   ProfScope ps(s, kid);
   if (DB)
-    hipLaunchKernelGGL((lstm_cell_h3db_kernel<KIND, RW, WAVES, ABL, PIPE, PRECISE, MS>), dim3(grid),
+    hipLaunchKernelGGL((lstm_cell_h3db_kernel<KIND, RW, WAVES, ABL, PIPE, PRECISE, MS, PROD>), dim3(grid),
                        dim3(C::THREADS), lds, s, ak, inv_scale);
   else
-    hipLaunchKernelGGL((lstm_cell_h3_kernel<KIND, RW, WAVES, ABL, PIPE, PRECISE, MS>), dim3(grid),
+    hipLaunchKernelGGL((lstm_cell_h3_kernel<KIND, RW, WAVES, ABL, PIPE, PRECISE, MS, PROD>), dim3(grid),
                        dim3(C::THREADS), lds, s, ak, inv_scale);
   return hipGetLastError();
 }
 // The training sweep (a.z_out set: the record for the BPTT) runs the unbiased gate activations
 // (PRECISE, device_common.h); the inference sweep the fast ones.
 template <int KIND, int RW = CellDef<KIND>::H3RW, int WAVES = CellDef<KIND>::H3WAVES, int ABL = 0,
-          int DB = CellDef<KIND>::H3DB, int PIPE = CellDef<KIND>::H3PIPE, int MS = CellDef<KIND>::H3MS>
+          int DB = CellDef<KIND>::H3DB, int PIPE = CellDef<KIND>::H3PIPE, int MS = CellDef<KIND>::H3MS,
+          int PROD = 3>
 static hipError_t run_cell_h3(const CellArgs& a, const float* inv_scale, int cu, int kid,
                               hipStream_t s) {
-  if constexpr (KIND >= 5) {   // the pooled-h kinds: inference only (launch_unet_step)
+  if constexpr (KIND >= 5 || PROD != 3) {   // the pooled-h kinds and the fp16 mode: inference only (launch_unet_step)
     return a.z_out ? hipErrorInvalidValue
-                   : run_cell_h3_<KIND, RW, WAVES, ABL, DB, PIPE, false, MS>(a, inv_scale, cu, kid, s);
+                   : run_cell_h3_<KIND, RW, WAVES, ABL, DB, PIPE, false, MS, PROD>(a, inv_scale, cu, kid, s);
   } else {
     return a.z_out ? run_cell_h3_<KIND, RW, WAVES, ABL, DB, PIPE, true, MS>(a, inv_scale, cu, kid, s)
                    : run_cell_h3_<KIND, RW, WAVES, ABL, DB, PIPE, false, MS>(a, inv_scale, cu, kid, s);
@@ -966,15 +1019,22 @@ static int cell_shape(const CellArgs&, int) {
   const char* e = std::getenv("AARMVS_CELL_MS");
   return (e && *e) ? std::max(0, std::min(2, std::atoi(e))) : 0;
 }
-template <int KIND>
+template <int KIND, int PROD = 3>
 static hipError_t run_cell(const CellArgs& a, const float* inv_scale, int cu, int kid, hipStream_t s) {
   using D = CellDef<KIND>;
   if constexpr (D::HID >= 16) {
     const int sh = cell_shape<KIND>(a, cu);
-    if (sh == 1) return run_cell_h3<KIND, 1, 8, 0, D::H3DB, D::H3PIPE, 2>(a, inv_scale, cu, kid, s);
-    if (sh == 2) return run_cell_h3<KIND, 1, 16, 0, D::H3DB, D::H3PIPE, 2>(a, inv_scale, cu, kid, s);
+    if (sh == 1) return run_cell_h3<KIND, 1, 8, 0, D::H3DB, D::H3PIPE, 2, PROD>(a, inv_scale, cu, kid, s);
+    if (sh == 2) return run_cell_h3<KIND, 1, 16, 0, D::H3DB, D::H3PIPE, 2, PROD>(a, inv_scale, cu, kid, s);
   }
-  return run_cell_h3<KIND>(a, inv_scale, cu, kid, s);
+  return run_cell_h3<KIND, D::H3RW, D::H3WAVES, 0, D::H3DB, D::H3PIPE, D::H3MS, PROD>(a, inv_scale, cu, kid, s);
+}
+// the cell in the sweep's precision mode (aarmvs_precision): the fp16 mode's 1-product variant
+// is timed under its own profiler name
+template <int KIND>
+static hipError_t run_cell_p(bool fp16, const CellArgs& a, const float* inv_scale, int cu, int kid, hipStream_t s) {
+  return fp16 ? run_cell<KIND, 1>(a, inv_scale, cu, kid + (K_CELL0_FP16 - K_CELL0), s)
+              : run_cell<KIND, 3>(a, inv_scale, cu, kid, s);
 }
 
 // ---------------------------------------------------------------------------
@@ -1119,13 +1179,17 @@ typedef _Float16 dhalf8 __attribute__((ext_vector_type(8)));
 // before use: 4 waves per SIMD instead of 3, 40 vs 48.6 us (deconv_1) and 16 vs 17.6 us
 // (deconv_0) per plane at the headline against the round-4 form (A fragments in registers,
 // each row's loads just before its MFMAs), bit-identical.
-template <int ABL = 0>
+// PROD 1 (the fp16 mode): the six hi fragments only, V converted once at the same 2^14, one
+// MFMA per product.
+template <int ABL = 0, int PROD = 3>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) deconv_mfma_kernel(const float* __restrict__ in,
                                                            const float* __restrict__ wfrag,
                                                            const float* __restrict__ bias, int Hi,
                                                            int Wi, float* __restrict__ out,
                                                            double* __restrict__ gn_part) {
-  __shared__ dhalf8 afs[12 * 64];
+  constexpr int NF = PROD == 3 ? 2 : 1;   // fragments per tap pair in LDS: hi (, lo)
+  static_assert(PROD == 3 || PROD == 1, "three split products or one");
+  __shared__ dhalf8 afs[6 * NF * 64];
   __shared__ double red[4 * 4];
   const int b = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int x0 = blockIdx.x * kDpTW;
@@ -1133,7 +1197,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) d
   const int Wo = 2 * Wi;
   const float* ib = in + (size_t)b * 16 * Hi * Wi;
   const dhalf8* af = reinterpret_cast<const dhalf8*>(wfrag);
-  for (int i = tid; i < 12 * 64; i += 256) afs[i] = af[i];
+  for (int i = tid; i < 6 * NF * 64; i += 256) afs[i] = PROD == 3 ? af[i] : af[(i >> 6) * 128 + (i & 63)];
   const float inv = wfrag[6 * 2 * 64 * 8 / 2] * (1.0f / 16384.0f);
   const int iy0 = blockIdx.y * kDpTH + wave * 2, ix = x0 + n;
   float4 raw[3][2][2];   // [input row iy0 + r][column ix + c][channel quad]
@@ -1156,13 +1220,19 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) d
     const float v[8] = {q[0].x, q[0].y, q[0].z, q[0].w, q[1].x, q[1].y, q[1].z, q[1].w};
 #pragma unroll
     for (int j = 0; j < 8; j += 2) {
-      uint32_t lo;
-      const half2_t hi = __builtin_bit_cast(half2_t, h3_split2(v[j] * 16384.0f, v[j + 1] * 16384.0f, lo));
-      const half2_t lw = __builtin_bit_cast(half2_t, lo);
-      bh[j] = hi[0];
-      bh[j + 1] = hi[1];
-      bl[j] = lw[0];
-      bl[j + 1] = lw[1];
+      if constexpr (PROD == 3) {
+        uint32_t lo;
+        const half2_t hi = __builtin_bit_cast(half2_t, h3_split2(v[j] * 16384.0f, v[j + 1] * 16384.0f, lo));
+        const half2_t lw = __builtin_bit_cast(half2_t, lo);
+        bh[j] = hi[0];
+        bh[j + 1] = hi[1];
+        bl[j] = lw[0];
+        bl[j + 1] = lw[1];
+      } else {   // (bl stays unset and unused)
+        const half2_t hi = __builtin_bit_cast(half2_t, h3_pack2(v[j] * 16384.0f, v[j + 1] * 16384.0f));
+        bh[j] = hi[0];
+        bh[j + 1] = hi[1];
+      }
     }
   };
   double part[4] = {0.0, 0.0, 0.0, 0.0};   // fp64 GroupNorm partials (E[x^2] - E[x]^2 cancels)
@@ -1181,10 +1251,13 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) d
       for (int r = 0; r < 16; ++r) a01[r] = a23[r] = 0.f;
       if (!(ABL & 2)) {
         auto mm = [&](fx16 acc, int p, dhalf8 bh, dhalf8 bl) {
-          const dhalf8 ah = afs[(p * 2 + 0) * 64 + lane], al = afs[(p * 2 + 1) * 64 + lane];
+          const dhalf8 ah = afs[(p * NF + 0) * 64 + lane];
           acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
+          if constexpr (PROD == 3) {
+            const dhalf8 al = afs[(p * NF + 1) * 64 + lane];
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc, 0, 0, 0);
+          }
           return acc;
         };
         a01 = mm(a01, 0, b00h, b00l);
@@ -1502,10 +1575,17 @@ UnetIO unet_io_record(const TrainLayout& T, const aarmvs_train_record& r, int d)
 }
 
 hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom& g,
-                            const Workspace& ws, const UnetIO& io, hipStream_t s, int stages) {
+                            const Workspace& ws, const UnetIO& io, hipStream_t s, int stages, int precision) {
   const ParamLayout& L = param_layout();
   const int H = g.H, W = g.W, B = g.B, cu = g.cu_count;
   hipError_t e;
+  // AARMVS_PREC_FP16: the 1-product cells and deconvs (inference only: the BPTT differentiates
+  // the split cells, so a step that writes a training record is refused)
+  if (precision != AARMVS_PREC_SPLIT && precision != AARMVS_PREC_FP16) return hipErrorInvalidValue;
+  const bool fp16 = precision == AARMVS_PREC_FP16;
+  if (fp16)
+    for (int k = 0; k < 5; ++k)
+      if (io.z[k]) return hipErrorInvalidValue;
   auto cell = [&](int k, std::initializer_list<ChanSrc> parts, int scale) {
     CellArgs a{};
     int i = 0;
@@ -1540,6 +1620,7 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
     const char* v = std::getenv("AARMVS_CELL_POOL");   // read once: the units of one plane agree
     return !(v && *v) || std::atoi(v) != 0;
   }();
+  const auto deconv = fp16 ? deconv_mfma_kernel<0, 1> : deconv_mfma_kernel<0, 3>;
   const bool pooled = pool_env && io.h_pool[0] && io.h_pool[1] && !io.z[0] && !io.z[1] && !io.z[2];
   if (stages & 1) {
   // cell 0: [x, h0] @ H
@@ -1547,8 +1628,8 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
                          {io.h_prev[0], 16, SRC_PLAIN, nullptr, nullptr, nullptr}}, 1);
   a0.xbound = ws.xbound;
   a0.h_pool = pooled ? io.h_pool[0] : nullptr;
-  e = pooled ? run_cell<5>(a0, params + L.h3_scale_off + 0, cu, K_CELL0, s)
-             : run_cell<0>(a0, params + L.h3_scale_off + 0, cu, K_CELL0, s);
+  e = pooled ? run_cell_p<5>(fp16, a0, params + L.h3_scale_off + 0, cu, K_CELL0, s)
+             : run_cell_p<0>(fp16, a0, params + L.h3_scale_off + 0, cu, K_CELL0, s);
   if (e != hipSuccess) return e;
   }
   if (stages & 2) {
@@ -1556,16 +1637,16 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
   CellArgs a1 = cell(1, {{pooled ? io.h_pool[0] : io.h_new[0], 16, pooled ? SRC_PLAIN : SRC_POOL, nullptr, nullptr, nullptr},
                          {io.h_prev[1], 16, SRC_PLAIN, nullptr, nullptr, nullptr}}, 2);
   a1.h_pool = pooled ? io.h_pool[1] : nullptr;
-  e = pooled ? run_cell<6>(a1, params + L.h3_scale_off + 1, cu, K_CELL1, s)
-             : run_cell<1>(a1, params + L.h3_scale_off + 1, cu, K_CELL1, s);
+  e = pooled ? run_cell_p<6>(fp16, a1, params + L.h3_scale_off + 1, cu, K_CELL1, s)
+             : run_cell_p<1>(fp16, a1, params + L.h3_scale_off + 1, cu, K_CELL1, s);
   if (e != hipSuccess) return e;
   }
   if (stages & 4) {
   // cell 2: [maxpool(h1'), h2] @ H/4
   CellArgs a2 = cell(2, {{pooled ? io.h_pool[1] : io.h_new[1], 16, pooled ? SRC_PLAIN : SRC_POOL, nullptr, nullptr, nullptr},
                          {io.h_prev[2], 16, SRC_PLAIN, nullptr, nullptr, nullptr}}, 4);
-  e = pooled ? run_cell<7>(a2, params + L.h3_scale_off + 2, cu, K_CELL2, s)
-             : run_cell<2>(a2, params + L.h3_scale_off + 2, cu, K_CELL2, s);
+  e = pooled ? run_cell_p<7>(fp16, a2, params + L.h3_scale_off + 2, cu, K_CELL2, s)
+             : run_cell_p<2>(fp16, a2, params + L.h3_scale_off + 2, cu, K_CELL2, s);
   if (e != hipSuccess) return e;
   }
   // GroupNorm statistics are per batch element, so the two cells that consume the deconvs'
@@ -1578,9 +1659,10 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
     const int Hi = H / 4, Wi = W / 4;
     const dim3 grid((Wi + kDpTW - 1) / kDpTW, (Hi + kDpTH - 1) / kDpTH, B);
     {
-      ProfScope ps(s, K_DECONV0);
-      hipLaunchKernelGGL(deconv_mfma_kernel<0>, grid, dim3(256), 0, s, io.h_new[2], params + L.dcm_off[0],
-                         params + L.pk_off[P_D0B], Hi, Wi, io.u0, ws.reg_part0);
+      ProfScope ps(s, fp16 ? K_DECONV0_FP16 : K_DECONV0);
+      hipLaunchKernelGGL(deconv, grid, dim3(256), 0, s,
+                         io.h_new[2], params + L.dcm_off[0], params + L.pk_off[P_D0B], Hi, Wi, io.u0,
+                         ws.reg_part0);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     nblk0 = (int)(grid.x * grid.y);
@@ -1596,7 +1678,7 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
                            {io.h_prev[3] + b * 16 * hq, 16, SRC_PLAIN, nullptr, nullptr, nullptr}},
                        2);
     per_b(a3, b, hq, 16);
-    if ((e = run_cell<3>(a3, params + L.h3_scale_off + 3, cu, K_CELL3, s)) != hipSuccess) return e;
+    if ((e = run_cell_p<3>(fp16, a3, params + L.h3_scale_off + 3, cu, K_CELL3, s)) != hipSuccess) return e;
   }
   }
   if (!(stages & 16)) return hipSuccess;
@@ -1606,9 +1688,10 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
     const int Hi = H / 2, Wi = W / 2;
     const dim3 grid((Wi + kDpTW - 1) / kDpTW, (Hi + kDpTH - 1) / kDpTH, B);
     {
-      ProfScope ps(s, K_DECONV1);
-      hipLaunchKernelGGL(deconv_mfma_kernel<0>, grid, dim3(256), 0, s, io.h_new[3], params + L.dcm_off[1],
-                         params + L.pk_off[P_D1B], Hi, Wi, io.u1, ws.reg_part);
+      ProfScope ps(s, fp16 ? K_DECONV1_FP16 : K_DECONV1);
+      hipLaunchKernelGGL(deconv, grid, dim3(256), 0, s,
+                         io.h_new[3], params + L.dcm_off[1], params + L.pk_off[P_D1B], Hi, Wi, io.u1,
+                         ws.reg_part);
     }
     if ((e = hipGetLastError()) != hipSuccess) return e;
     nblk1 = (int)(grid.x * grid.y);
@@ -1624,7 +1707,7 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
                            {io.h_prev[4] + b * 8 * hw, 8, SRC_PLAIN, nullptr, nullptr, nullptr}},
                        1);
     per_b(a4, b, hw, 8);
-    if ((e = run_cell<4>(a4, params + L.h3_scale_off + 4, cu, K_CELL4, s)) != hipSuccess) return e;
+    if ((e = run_cell_p<4>(fp16, a4, params + L.h3_scale_off + 4, cu, K_CELL4, s)) != hipSuccess) return e;
   }
   return hipSuccess;
 }

@@ -347,8 +347,15 @@ class EMVSNet(nn.Module):
                      "warp gather/scatter) on gfx950")
 
     def __init__(self, disparity_level, image_scale=0.25, max_h=960, max_w=480, return_depth=False,
-                 evidential=True, return_cost=False, checkpoint_planes=0):
+                 evidential=True, return_cost=False, checkpoint_planes=0, sweep_precision="split"):
         super().__init__()
+        # precision of the regulariser's convs on the return_depth=True (inference) path only:
+        # "split" (parity) or "fp16" (aarmvs.ops.DepthSweep); the other forwards, training
+        # included, always run the split mode
+        if sweep_precision not in _ops.DepthSweep.PRECISIONS:
+            raise ValueError(f"EMVSNet: sweep_precision must be one of "
+                             f"{sorted(_ops.DepthSweep.PRECISIONS)}, got {sweep_precision!r}")
+        self.sweep_precision = sweep_precision
         # plane-segment checkpointing of the training sweep (_SweepTrainCkpt): 0 keeps the whole
         # record (_SweepTrain); S > 0 keeps an S-plane record and recomputes each segment's
         # forward before its backward.  Multiples of 16 only: the backward's 16-plane groups must
@@ -406,6 +413,7 @@ class EMVSNet(nn.Module):
         B, C, H, W = ref.shape
         self._check_geometry(H, W)
         sweep = self._sweep(ref.device)
+        sweep.precision = self.sweep_precision if self.return_depth else "split"
         dv = depth_values.float()
         # the reference head runs at B == 1, D == 32 only
         evidential_on = not isinstance(self.evidential, EvidentialUnavailable) and (

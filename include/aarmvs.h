@@ -199,6 +199,32 @@ int aarmvs_train_segment_bytes(int B, int H, int W, int nsrc, int planes, size_t
 
 size_t aarmvs_sweep_workspace_bytes(int B, int H, int W, int nsrc);
 int aarmvs_sweep(const aarmvs_sweep_args* args, hipStream_t stream);
+
+/* Precision of the regulariser's matrix products in an inference sweep.
+ * AARMVS_PREC_SPLIT (the default and the parity mode): every fp32 product of the five ConvLSTM
+ * convs and the two transposed convs is three fp16 matrix products with fp32 accumulation
+ * (w_hi x_hi + w_hi x_lo + w_lo x_hi, ~2^-21 relative per product).
+ * AARMVS_PREC_FP16 (opt-in): one product, w_hi x_hi.  What is rounded: the operands of those
+ * seven convs only -- the weights (the hi planes of the same packed buffer) and the staged
+ * inputs (cat[x, h] of a cell after the fused max-pool / GroupNorm+ReLU; the deconv's input h)
+ * -- each once, to fp16's 11 significant bits, round to nearest even, at the power-of-two
+ * scale the split mode stages it at (weights: max|w| 2^e in [2^13, 2^14]; h: 2^12 in the
+ * cells, 2^14 in the deconvs; cell 0's cost slice and cells 3 and 4's GroupNorm part: the
+ * scale that puts their bound in [2^14, 2^15)), so the fp16 range guards hold as before and the
+ * rounding is relative (2^-12 per operand) for all but values 2^-28 below the bound.  What is
+ * not: accumulation, bias, gate math, the c and h state, the GroupNorm statistics, the head,
+ * the winner-take-all, the omega network and the cost slice all stay fp32 as in the split mode.
+ * Workspace size, stream schedule, d_range behaviour and determinism are the split mode's.
+ * Inference only: with a training record the call returns AARMVS_ERR_INVALID (the BPTT
+ * differentiates the split cells).  Measured errors and speed: DESIGN.md §7. */
+typedef enum aarmvs_precision {
+  AARMVS_PREC_SPLIT = 0,
+  AARMVS_PREC_FP16 = 1
+} aarmvs_precision;
+/* aarmvs_sweep at a precision (an aarmvs_precision value; anything else: AARMVS_ERR_INVALID).
+ * aarmvs_sweep(a, s) is aarmvs_sweep_p(a, AARMVS_PREC_SPLIT, s).  The mode is a parameter of
+ * the call, not a field of aarmvs_sweep_args, so the struct keeps its size. */
+int aarmvs_sweep_p(const aarmvs_sweep_args* args, int precision, hipStream_t stream);
 /* A stream for aux_stream owned by the library (one per device, created on first use, never
  * destroyed): a process gets four hardware queues and streams beyond four share them, so a
  * caller without streams of its own passes this one rather than creating a fifth (the library's
@@ -277,6 +303,10 @@ float* aarmvs_state_ptr(void* workspace, int B, int H, int W, int nsrc, int plan
 int aarmvs_unet_step(const float* x, int B, int H, int W, int nsrc, int step,
                      const void* packed_params, void* workspace, float* cost_out,
                      hipStream_t stream);
+/* The same at a precision (aarmvs_precision); aarmvs_unet_step is the AARMVS_PREC_SPLIT form. */
+int aarmvs_unet_step_p(const float* x, int B, int H, int W, int nsrc, int step,
+                       const void* packed_params, void* workspace, float* cost_out, int precision,
+                       hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
  * One plane's cost slice (SURVEY §8b aarmvs_cost_slice): replaces, for one depth
