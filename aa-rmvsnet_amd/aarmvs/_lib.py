@@ -45,6 +45,12 @@ class SweepArgs(ctypes.Structure):
     ]
 
 
+class RefineArgs(ctypes.Structure):
+    """Mirror of ``aarmvs_refine_args``."""
+    _fields_ = [("state", c_void_p), ("depth_refined_out", c_void_p), ("conf_window_out", c_void_p),
+                ("index_out", c_void_p)]
+
+
 class BackwardArgs(ctypes.Structure):
     """Mirror of ``aarmvs_backward_args``."""
     _fields_ = [
@@ -121,6 +127,8 @@ SIGNATURES = {
     "aarmvs_sweep_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "aarmvs_sweep": (c_int, [ctypes.POINTER(SweepArgs), c_void_p]),
     "aarmvs_sweep_p": (c_int, [ctypes.POINTER(SweepArgs), c_int, c_void_p]),
+    "aarmvs_refine_state_bytes": (c_size_t, [c_int, c_int]),
+    "aarmvs_sweep_r": (c_int, [ctypes.POINTER(SweepArgs), c_int, ctypes.POINTER(RefineArgs), c_void_p]),
     "aarmvs_aux_stream": (c_int, [ctypes.POINTER(c_void_p)]),
     "aarmvs_train_record_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "aarmvs_train_segment_bytes": (c_int, [c_int] * 5 + [ctypes.POINTER(c_size_t)] * 2),
@@ -147,6 +155,9 @@ SIGNATURES = {
                                   c_void_p]),
     "aarmvs_wta_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                   c_void_p]),
+    "aarmvs_wta_refine_update": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),
+    "aarmvs_wta_refine_finalize": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 4),
+    "aarmvs_refine_from_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
     "aarmvs_fusion_filter": (c_int, [ctypes.POINTER(FusionArgs), c_void_p]),
     "aarmvs_pyr_down": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "aarmvs_fusion_points_workspace_bytes": (c_size_t, [c_int, c_int]),

@@ -13,6 +13,9 @@ Outputs per sample, as eval.py names them (``filename.format(kind, ext)``):
                             (eval.py writes nothing there: its head raises for D != 32)
   confidence_0/<ref>.pfm    photometric confidence (max prob / exp sum)
   epistemic_0/, aleatoric_0/  where the head runs: 1/sqrt(nu), sqrt(beta (nu+1) / (nu alpha))
+  depth_refined_0/, confidence_window_0/  with --refine_depth (not in eval.py): the sweep's
+                            sub-plane depth and windowed confidence (include/aarmvs.h,
+                            aarmvs_sweep_r), always the sweep's, also where the head runs
 eval.py's PNG previews are not written (data_io.save_png is broken on numpy >= 1.24,
 SURVEY §8f-4).
 
@@ -55,6 +58,8 @@ def parse_args(argv=None):
     ap.add_argument("--outdir", default="./outputs")
     # not in eval.py: the regulariser's precision mode (aarmvs.ops.DepthSweep)
     ap.add_argument("--sweep_precision", choices=("split", "fp16"), default="split")
+    # not in eval.py: also write the sub-plane refined depth and the windowed confidence
+    ap.add_argument("--refine_depth", action="store_true")
     return ap.parse_args(argv)
 
 
@@ -95,7 +100,8 @@ def save_depth(args, rank: int = 0, world: int = 1, device=None, model=None) -> 
     if model is None:
         model = EMVSNet(disparity_level=32, image_scale=args.image_scale, max_h=args.max_h,
                         max_w=args.max_w, return_depth=True,
-                        sweep_precision=getattr(args, "sweep_precision", "split"))
+                        sweep_precision=getattr(args, "sweep_precision", "split"),
+                        refine_depth=getattr(args, "refine_depth", False))
         if args.loadckpt:
             load_checkpoint(model, args.loadckpt)
     model = model.to(device).eval()
@@ -109,9 +115,16 @@ def save_depth(args, rank: int = 0, world: int = 1, device=None, model=None) -> 
             conf = out["photometric_confidence"].cpu().numpy()
             ev = out["evidential_prediction"]
             ev = None if ev is None else ev.cpu().numpy()
+            refined = None
+            if getattr(args, "refine_depth", False):
+                if "depth_refined" not in out:
+                    raise ValueError("eval_sharded: --refine_depth needs a model built with refine_depth=True")
+                refined = {"depth_refined": out["depth_refined"].cpu().numpy(),
+                           "confidence_window": out["photometric_confidence_window"].cpu().numpy()}
             for b, filename in enumerate(sample["filename"]):
                 path = lambda kind: os.path.join(save_dir, filename.format(kind + "_0", ".pfm"))
-                for kind in ("depth_est", "confidence") + (("epistemic", "aleatoric") if ev is not None else ()):
+                for kind in (("depth_est", "confidence") + (("epistemic", "aleatoric") if ev is not None else ())
+                             + (tuple(refined) if refined is not None else ())):
                     os.makedirs(os.path.dirname(path(kind)), exist_ok=True)
                 if ev is not None:   # eval.py:143-160 (B == 1)
                     gamma, nu, alpha, beta = ev[0], ev[1], ev[2], ev[3]
@@ -121,6 +134,8 @@ def save_depth(args, rank: int = 0, world: int = 1, device=None, model=None) -> 
                 else:
                     save_pfm(path("depth_est"), np.ascontiguousarray(depth[b], np.float32))
                 save_pfm(path("confidence"), np.ascontiguousarray(conf[b], np.float32))
+                for kind, maps in (refined or {}).items():
+                    save_pfm(path(kind), np.ascontiguousarray(maps[b], np.float32))
                 written.append(filename)
     return written
 

@@ -33,6 +33,9 @@ from datasets.data_io import read_pfm, save_pfm  # noqa: F401  (fusion.read_pfm 
 from . import _lib
 from ._lib import AarmvsError, check, lib
 
+# the per-scan folders the drivers read the maps from (the reference's names, eval.py)
+DEFAULT_DEPTH_DIR, DEFAULT_CONF_DIR = "depth_est_0", "confidence_0"
+
 
 def pack_cameras(ref_cam, src_cams) -> np.ndarray:
     """float32 matrices exactly as numpy forms them in fusion.py:71-108 (float32 inverses
@@ -157,22 +160,27 @@ def resize_linear(img, width, height):
     return out.astype(np.float32)
 
 
-def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="cuda"):
+def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="cuda",
+                 depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR):
     """fusion.py:135-273 for one scan: for every (ref_view, src_views) of pair.txt with an
     estimated depth map, the geometric / photometric filtering on the GPU
     (``filter_depth_core``), the three mask PNGs under out_folder/mask, and the kept pixels'
     world points (coloured from the rescaled, cropped reference image) written to
-    plyfilename.  Returns the number of points written."""
+    plyfilename.  Returns the number of points written.  ``depth_dir`` / ``conf_dir``: the
+    folders under out_folder the depth and confidence maps are read from (the reference's
+    depth_est_0 / confidence_0; e.g. eval_sharded --refine_depth's depth_refined_0 /
+    confidence_window_0)."""
     vertexs, vertex_colors = [], []
     dev = torch.device(device)
+    depth_file = os.path.join(out_folder, depth_dir, "{:0>8}.pfm")
     for ref_view, src_views in read_pair_file(os.path.join(scan_folder, "pair.txt")):
-        dpath = os.path.join(out_folder, "depth_est_0/{:0>8}.pfm".format(ref_view))
+        dpath = depth_file.format(ref_view)
         if not os.path.exists(dpath):
             print("skip", ref_view)
             continue
         ref_img = read_img(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref_view)))
         ref_depth_est = read_pfm(dpath)[0]
-        confidence = read_pfm(os.path.join(out_folder, "confidence_0/{:0>8}.pfm".format(ref_view)))[0]
+        confidence = read_pfm(os.path.join(out_folder, conf_dir, "{:0>8}.pfm".format(ref_view)))[0]
         scale, index, index_p, flag = crop_params(ref_img.shape[:2], confidence.shape[:2])
         ref_img = resize_linear(ref_img, int(ref_img.shape[1] * scale), int(ref_img.shape[0] * scale))
         if flag == 0:
@@ -184,7 +192,7 @@ def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="
         src_depths, src_cams = [], []
         for src_view in src_views:
             src_depths.append(torch.from_numpy(np.ascontiguousarray(read_pfm(
-                os.path.join(out_folder, "depth_est_0/{:0>8}.pfm".format(src_view)))[0])).to(dev))
+                depth_file.format(src_view))[0])).to(dev))
             src_cams.append(read_camera_parameters(cam_file.format(src_view), scale, index, flag))
         photo, geo, final, avg = filter_depth_core(
             torch.from_numpy(np.ascontiguousarray(ref_depth_est)).to(dev),
@@ -305,7 +313,8 @@ def read_camera_parameters_tnt(filename):
     return intrinsics, extrinsics
 
 
-def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, device="cuda"):
+def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, device="cuda",
+                     depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR):
     """fusion_padding.py:137-266 for one scan.  Per reference view of pair.txt: the image goes
     to the GPU and through ``pyr_down``; rows [2:-2] are cropped from the reference and source
     depth maps and the confidence map (the padding loader's extra rows); ``filter_depth_core``
@@ -313,11 +322,12 @@ def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, 
     fusion_padding.py's fixed one); ``fuse_points_gpu`` extracts the kept
     points.  Only the three masks (for the PNGs under out_folder/mask) and the kept points come
     back to the host.  Writes plyfilename and returns the number of points.  A reference view
-    without a depth map is skipped (the reference stops with an error there)."""
+    without a depth map is skipped (the reference stops with an error there).  ``depth_dir`` /
+    ``conf_dir``: as for ``filter_depth``."""
     vertexs, vertex_colors = [], []
     dev = torch.device(device)
     cam_file = os.path.join(scan_folder, "cams/{:0>8}_cam.txt")
-    depth_file = os.path.join(out_folder, "depth_est_0/{:0>8}.pfm")
+    depth_file = os.path.join(out_folder, depth_dir, "{:0>8}.pfm")
     cache = {}
 
     def cropped(path):
@@ -336,7 +346,7 @@ def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, 
         ref_img = pyr_down(torch.from_numpy(
             read_img(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref_view)))).to(dev))
         ref_depth_est = depth_of(ref_view)
-        confidence = cropped(os.path.join(out_folder, "confidence_0/{:0>8}.pfm".format(ref_view)))
+        confidence = cropped(os.path.join(out_folder, conf_dir, "{:0>8}.pfm".format(ref_view)))
         if tuple(ref_img.shape[:2]) != tuple(ref_depth_est.shape):
             raise AarmvsError(f"aarmvs: view {ref_view}: the halved image is {tuple(ref_img.shape[:2])} "
                               f"but the cropped depth map is {tuple(ref_depth_est.shape)}")
@@ -439,6 +449,10 @@ def build_parser():
     p.add_argument("--outdir", required=True, help="folder of the per-scan depth_est_0/ and confidence_0/")
     p.add_argument("--photo_threshold", type=float, default=None,
                    help="confidence threshold (default: 0.35 for dtu, 0.3 for tnt)")
+    p.add_argument("--depth_dir", default=DEFAULT_DEPTH_DIR,
+                   help="per-scan folder of the depth maps (e.g. depth_refined_0 of eval_sharded --refine_depth)")
+    p.add_argument("--conf_dir", default=DEFAULT_CONF_DIR,
+                   help="per-scan folder of the confidence maps (e.g. confidence_window_0)")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -467,10 +481,15 @@ def main(argv=None):
         scan_folder = os.path.join(args.testpath, scan)
         out_folder = os.path.join(args.outdir, scan)
         ply = ply_path(args.outdir, scan, args.test_dataset)
+        # (the folders are passed on only when they are not the defaults: the default call is
+        # the five-argument one it has always been)
+        dirs = {}
+        if (args.depth_dir, args.conf_dir) != (DEFAULT_DEPTH_DIR, DEFAULT_CONF_DIR):
+            dirs = dict(depth_dir=args.depth_dir, conf_dir=args.conf_dir)
         if args.test_dataset == "tnt":
-            filter_depth_tnt(scan_folder, out_folder, ply, args.photo_threshold, args.device)
+            filter_depth_tnt(scan_folder, out_folder, ply, args.photo_threshold, args.device, **dirs)
         else:
-            filter_depth(scan_folder, out_folder, ply, args.photo_threshold, args.device)
+            filter_depth(scan_folder, out_folder, ply, args.photo_threshold, args.device, **dirs)
 
 
 if __name__ == "__main__":

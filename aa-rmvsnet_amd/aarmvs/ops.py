@@ -475,6 +475,95 @@ def wta_update(cost: torch.Tensor, depth_d: torch.Tensor, max_prob: torch.Tensor
                                   _stream()), "wta_update")
 
 
+def refine_state(B: int, HW: int, device) -> torch.Tensor:
+    """A state buffer of the sub-plane refinement (aarmvs_refine_state_bytes: 16 B per pixel)."""
+    n = lib().aarmvs_refine_state_bytes(B, HW)
+    if n == 0:
+        raise AarmvsError(f"aarmvs: refine state geometry B={B} HW={HW}")
+    return torch.empty(n // 4, dtype=torch.int32, device=device)
+
+
+def _check_refine_state(state: torch.Tensor, B: int, HW: int, device) -> None:
+    if (not torch.is_tensor(state) or not state.is_cuda or state.device != device or not state.is_contiguous()
+            or state.numel() * state.element_size() < lib().aarmvs_refine_state_bytes(B, HW)):
+        raise AarmvsError(f"aarmvs: the refine state must be a contiguous tensor of {16 * B * HW} B on {device} "
+                          "(ops.refine_state(B, HW, device))")
+
+
+@_on_tensor_device
+def wta_refine_update(cost: torch.Tensor, d: int, depth_d: torch.Tensor, max_prob: torch.Tensor,
+                      depth_map: torch.Tensor, exp_sum: torch.Tensor, state: torch.Tensor) -> None:
+    """``wta_update`` of plane ``d`` (planes in order from 0) that also keeps the sub-plane
+    refinement's ``state`` (``refine_state(B, H*W, device)``; d == 0 resets it), in place
+    (aarmvs_wta_refine_update)."""
+    ts = (cost, max_prob, depth_map, exp_sum)
+    _require_device(*ts)
+    B = cost.shape[0]
+    for t in ts:
+        if t.shape != cost.shape or not t.is_contiguous() or t.device != cost.device:
+            raise AarmvsError("aarmvs: wta_refine_update needs contiguous tensors of one [B,H,W] shape")
+    HW = cost[0].numel()
+    _check_refine_state(state, B, HW, cost.device)
+    dep = depth_d.reshape(-1).to(cost.device, torch.float32).contiguous()
+    if dep.numel() != B:
+        raise AarmvsError(f"aarmvs: depth_d must hold B={B} values")
+    if int(d) < 0:
+        raise AarmvsError(f"aarmvs: plane index {d} < 0")
+    check(lib().aarmvs_wta_refine_update(cost.data_ptr(), int(d), max_prob.data_ptr(), depth_map.data_ptr(),
+                                         exp_sum.data_ptr(), state.data_ptr(), dep.data_ptr(), B, HW,
+                                         _stream()), "wta_refine_update")
+
+
+@_on_tensor_device
+def wta_refine_finalize(max_prob: torch.Tensor, depth_map: torch.Tensor, exp_sum: torch.Tensor,
+                        state: torch.Tensor, depth_values: torch.Tensor, n: int) -> dict:
+    """{'depth_refined', 'conf_window' (float32), 'index' (int32)}, each shaped like ``max_prob``
+    [B,H,W], after ``n`` planes of ``wta_refine_update`` (aarmvs_wta_refine_finalize);
+    depth_values [B,D]."""
+    ts = (max_prob, depth_map, exp_sum)
+    _require_device(*ts)
+    for t in ts:
+        if t.shape != max_prob.shape or not t.is_contiguous() or t.device != max_prob.device:
+            raise AarmvsError("aarmvs: wta_refine_finalize needs contiguous tensors of one [B,H,W] shape")
+    B, HW = max_prob.shape[0], max_prob[0].numel()
+    _check_refine_state(state, B, HW, max_prob.device)
+    if depth_values.dim() != 2 or depth_values.shape[0] != B:
+        raise AarmvsError(f"aarmvs: depth_values must be [B={B},D], got {tuple(depth_values.shape)}")
+    dv = depth_values.to(max_prob.device, torch.float32).contiguous()
+    D = dv.shape[1]
+    if not 1 <= int(n) <= D:
+        raise AarmvsError(f"aarmvs: n = {n} planes outside [1, D={D}]")
+    out = {"depth_refined": torch.empty_like(max_prob), "conf_window": torch.empty_like(max_prob),
+           "index": torch.empty(max_prob.shape, dtype=torch.int32, device=max_prob.device)}
+    check(lib().aarmvs_wta_refine_finalize(max_prob.data_ptr(), depth_map.data_ptr(), exp_sum.data_ptr(),
+                                           state.data_ptr(), dv.data_ptr(), B, D, int(n), HW,
+                                           out["depth_refined"].data_ptr(), out["conf_window"].data_ptr(),
+                                           out["index"].data_ptr(), _stream()), "wta_refine_finalize")
+    return out
+
+
+@_on_tensor_device
+def refine_from_cost(cost: torch.Tensor, depth_values: torch.Tensor) -> dict:
+    """The sub-plane refinement from a whole cost volume [B,D,H,W] and depth_values [B,D]
+    (aarmvs_refine_from_cost): {'depth_refined', 'conf_window' [B,H,W] float32, 'index' [B,H,W]
+    int32}, bit for bit what a sweep with ``want_refined`` gives on the same cost values."""
+    _require_device(cost)
+    c = cost.detach().contiguous()
+    if c.dim() != 4:
+        raise AarmvsError(f"aarmvs: refine_from_cost cost must be [B,D,H,W], got {tuple(c.shape)}")
+    B, D, H, W = c.shape
+    if tuple(depth_values.shape) != (B, D):
+        raise AarmvsError(f"aarmvs: depth_values must be [B={B},D={D}], got {tuple(depth_values.shape)}")
+    dv = depth_values.detach().to(c.device, torch.float32).contiguous()
+    out = {"depth_refined": torch.empty(B, H, W, device=c.device),
+           "conf_window": torch.empty(B, H, W, device=c.device),
+           "index": torch.empty(B, H, W, dtype=torch.int32, device=c.device)}
+    check(lib().aarmvs_refine_from_cost(c.data_ptr(), dv.data_ptr(), B, D, H * W,
+                                        out["depth_refined"].data_ptr(), out["conf_window"].data_ptr(),
+                                        out["index"].data_ptr(), _stream()), "refine_from_cost")
+    return out
+
+
 def aux_stream(device) -> torch.cuda.ExternalStream:
     """The library's aux stream of ``device`` (aarmvs_aux_stream): one per device, shared by every
     DepthSweep.  The process gets four hardware queues and streams beyond four share them (a
@@ -510,6 +599,7 @@ class DepthSweep:
         self.device = torch.device(device)
         self.packed = pack_params(params, self.device)
         self._ws = {}
+        self._refine = {}
         self._aux = None
         self.overlap = overlap
 
@@ -547,6 +637,16 @@ class DepthSweep:
             ws = torch.empty(n, dtype=torch.uint8, device=self.device)
             self._ws[key] = ws
         return ws
+
+    def refine_state(self, B, H, W) -> torch.Tensor:
+        """The sub-plane refinement's state of a (B, H, W) sweep (16 B per pixel), cached beside
+        the workspace, one geometry at a time: d_range calls with ``want_refined`` continue it."""
+        key = (B, H, W)
+        st = self._refine.get(key)
+        if st is None:
+            st = refine_state(B, H * W, self.device)
+            self._refine = {key: st}
+        return st
 
     def relative(self, ref_proj, src_projs, B: int) -> torch.Tensor:
         """[nsrc,B,12] device tensor of rows 0..2 of src_proj @ inv(ref_proj) per source view
@@ -644,8 +744,15 @@ class DepthSweep:
     @_on_tensor_device
     def __call__(self, ref_fea, src_feas, ref_proj, src_projs, depth_values, *,
                  want_depth=True, want_cost=False, d_range=None, debug=False, cost_out=None,
-                 rel=None, record=None, record_d0=0):
+                 rel=None, record=None, record_d0=0, want_refined=False):
         """Returns dict(depth, conf, cost, slice, omega) (entries None when not requested).
+
+        ``want_refined`` (opt-in, inference only) adds ``depth_refined`` and ``conf_window``
+        [B,H,W] and ``index`` [B,H,W] int32: the local expectation of depth over the winning
+        plane and its two neighbours, the probability mass of that window, and the winner's
+        plane (include/aarmvs.h, aarmvs_sweep_r).  They describe the planes up to the call's
+        last one; with ``d_range`` every call of the sweep must pass ``want_refined``, which
+        carries the state in ``self.refine_state(B, H, W)``.  The other outputs do not change.
 
         ``d_range=(d0, d1)`` runs planes d0..d1-1 only (d0 == 0 resets the hidden state;
         later ranges continue from the state the previous call left in the workspace).
@@ -715,6 +822,19 @@ class DepthSweep:
         a.omega_out = _ptr(out["omega"])
         a.aux_stream = self._aux.cuda_stream if self._aux is not None else None
         rec_struct = None
+        refine = None
+        if want_refined:
+            if record is not None:
+                raise AarmvsError("aarmvs: want_refined is an inference output; a recorded (training) sweep "
+                                  "has none (ops.refine_from_cost works on its cost volume)")
+            out["depth_refined"] = torch.empty(B, H, W, device=ref.device)
+            out["conf_window"] = torch.empty(B, H, W, device=ref.device)
+            out["index"] = torch.empty(B, H, W, dtype=torch.int32, device=ref.device)
+            refine = _lib.RefineArgs()
+            refine.state = self.refine_state(B, H, W).data_ptr()
+            refine.depth_refined_out = out["depth_refined"].data_ptr()
+            refine.conf_window_out = out["conf_window"].data_ptr()
+            refine.index_out = out["index"].data_ptr()
         if record is not None:
             if self._precision != "split":
                 raise AarmvsError(f"aarmvs: precision {self._precision!r} is an inference mode; a recorded "
@@ -722,7 +842,8 @@ class DepthSweep:
             rec_struct = self._segment_struct(a, record, record_d0, d0, d1, ref.device)
         elif record_d0:
             raise AarmvsError("aarmvs: record_d0 without a record")
-        check(lib().aarmvs_sweep_p(ctypes.byref(a), self.PRECISIONS[self._precision], _stream()), "sweep")
+        check(lib().aarmvs_sweep_r(ctypes.byref(a), self.PRECISIONS[self._precision],
+                                   ctypes.byref(refine) if refine is not None else None, _stream()), "sweep")
         out["_keepalive"] = (rel, dv, srcs, ref, rec_struct)
         return out
 

@@ -20,7 +20,9 @@ eval mode, no grad, the same loss as training and the six masked depth metrics
 (``aarmvs.ops.depth_metrics``) of the loss's depth map, averaged over batches as
 DictAverageMeter does.  Each rank takes its contiguous shard of the test samples
 (``aarmvs.dist.shard_range``); the per-batch sums and batch counts are all-reduced, rank 0
-prints ``avg_test_scalars:``.  The evidential scalars, tensorboard summaries and the image /
+prints ``avg_test_scalars:``.  ``--refine_metrics`` adds the same six metrics of the sub-plane
+refined depth (``aarmvs.ops.refine_from_cost`` on the pass's cost volume; not in train.py) on a
+line of their own, ``avg_test_scalars_refined:``.  The evidential scalars, tensorboard summaries and the image /
 .pt dumps of test_sample are not reproduced.
 
 usage: python -m torch.distributed.run --nproc-per-node 8 -m aarmvs.train_ddp \\
@@ -79,6 +81,9 @@ def parse_args(argv=None):
     ap.add_argument("--testlist", default=None, help="test list")
     ap.add_argument("--test_light_idx", type=int, default=3,
                     help="light index of the test images (train.py --light_idx: 3)")
+    ap.add_argument("--refine_metrics", action="store_true",
+                    help="with --testpath: also report the depth metrics of the sub-plane refined depth "
+                         "(the local expectation over the winning plane and its neighbours)")
     return ap.parse_args(argv)
 
 
@@ -102,21 +107,37 @@ def _loss_and_depth(out, s, fused: bool):
     return mvsnet_cls_loss(first, s["depth"], s["mask"], s["depth_values"])
 
 
-def run_test_pass(model, loader, device, fused: bool, rank: int = 0, log=print) -> dict:
+REFINED = "refined_"   # prefix of --refine_metrics' keys in run_test_pass's result
+
+
+def run_test_pass(model, loader, device, fused: bool, rank: int = 0, log=print, refine: bool = False) -> dict:
     """train.py:259-285 on this rank's loader: per batch the loss and the masked metrics of its
-    depth map, summed over batches and ranks, divided by the batch count."""
+    depth map, summed over batches and ranks, divided by the batch count.  ``refine``: also the
+    metrics of ops.refine_from_cost's depth, under REFINED-prefixed keys.  Its cost volume is the
+    model's with --fused_loss and the log of the probability volume otherwise (the same per-pixel
+    shift on every plane, which the refinement's quotient cancels)."""
     from . import ops
     keys = ["loss", "abs_depth_error"] + [f"thres{t}mm_error" for t in TEST_THRESHOLDS]
+    base = len(keys)
+    if refine:
+        keys = keys + [REFINED + k for k in keys[1:]]
     sums, count = [0.0] * len(keys), 0
     model.eval()
     with torch.no_grad():
         for sample in loader:
             s = {k: v.to(device) if torch.is_tensor(v) else v for k, v in sample.items()}
-            loss, depth_est = _loss_and_depth(model(s["imgs"], s["proj_matrices"], s["depth_values"]),
-                                              s, fused)
+            out = model(s["imgs"], s["proj_matrices"], s["depth_values"])
+            loss, depth_est = _loss_and_depth(out, s, fused)
             m = ops.depth_metrics(depth_est.float(), s["depth"].float(), s["mask"].float(),
                                   TEST_THRESHOLDS)
-            row = torch.stack([loss.double().reshape(())] + [m[k] for k in keys[1:]]).tolist()
+            cells = [loss.double().reshape(())] + [m[k] for k in keys[1:base]]
+            if refine:
+                cost = out[0] if getattr(model, "return_cost", False) else torch.log(out[0])
+                r = ops.refine_from_cost(cost.float(), s["depth_values"].float())
+                mr = ops.depth_metrics(r["depth_refined"], s["depth"].float(), s["mask"].float(),
+                                       TEST_THRESHOLDS)
+                cells += [mr[k[len(REFINED):]] for k in keys[base:]]
+            row = torch.stack(cells).tolist()
             sums = [a + b for a, b in zip(sums, row)]
             count += 1
     total = sum_over_ranks(sums + [float(count)], device)
@@ -126,7 +147,8 @@ def run_test_pass(model, loader, device, fused: bool, rank: int = 0, log=print) 
 
 def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
     """Runs train.py's epochs on this rank's shard; returns {'losses', 'checkpoints',
-    'test_scalars' (one dict per epoch when --testpath is given, else empty)}."""
+    'test_scalars' (one dict per epoch when --testpath is given, else empty)[,
+    'test_scalars_refined' likewise with --refine_metrics]}."""
     from datasets import find_dataset_def
     from models import EMVSNet
     device = torch.device(device or f"cuda:{local_device_index(env()[1])}")
@@ -179,7 +201,7 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
         sched.step()
     if rank == 0:
         os.makedirs(args.logdir, exist_ok=True)
-    losses, ckpts, test_scalars = [], [], []
+    losses, ckpts, test_scalars, test_scalars_refined = [], [], [], []
     for epoch in range(start_epoch, args.epochs):
         sampler.set_epoch(epoch)
         for step, sample in enumerate(loader):
@@ -208,10 +230,20 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
             # the bare module: ranks may hold different numbers of test batches, and DDP's
             # forward synchronises buffers across ranks
             core = model.module if isinstance(model, torch.nn.parallel.DistributedDataParallel) else model
-            test_scalars.append(run_test_pass(core, test_loader, device, args.fused_loss, rank, log))
+            scalars = run_test_pass(core, test_loader, device, args.fused_loss, rank, log,
+                                    refine=getattr(args, "refine_metrics", False))
+            test_scalars.append({k: v for k, v in scalars.items() if not k.startswith(REFINED)})
+            refined = {k[len(REFINED):]: v for k, v in scalars.items() if k.startswith(REFINED)}
+            if refined:
+                test_scalars_refined.append(refined)
             if rank == 0:
                 log("avg_test_scalars:", test_scalars[-1])
-    return {"losses": losses, "checkpoints": ckpts, "test_scalars": test_scalars}
+                if refined:
+                    log("avg_test_scalars_refined:", refined)
+    out = {"losses": losses, "checkpoints": ckpts, "test_scalars": test_scalars}
+    if test_scalars_refined:
+        out["test_scalars_refined"] = test_scalars_refined
+    return out
 
 
 def main(argv=None) -> int:

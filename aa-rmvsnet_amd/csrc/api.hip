@@ -101,7 +101,7 @@ static const char* kKernelNames[K_COUNT] = {
     "pyr_down", "fusion_points",
     "cls_loss_fwd", "cls_loss_reduce", "cls_loss_bwd", "depth_metrics",
     "lstm_cell0_fp16", "lstm_cell1_fp16", "lstm_cell2_fp16", "lstm_cell3_fp16", "lstm_cell4_fp16",
-    "deconv0_fp16", "deconv1_fp16"};
+    "deconv0_fp16", "deconv1_fp16", "refine"};
 
 static hipEvent_t prof_event() {
   if (g_prof_used == g_prof_pool.size()) {
@@ -682,6 +682,7 @@ struct HipSweep {
   hipEvent_t* ev;
   hipStream_t st[kSweepSlots];
   int precision = AARMVS_PREC_SPLIT;   // aarmvs_precision of the regulariser's units
+  void* refine_state = nullptr;        // aarmvs_refine_args.state: the head also keeps it
   int rc = 0, io_d = -1;
   UnetIO io_{};
 
@@ -757,7 +758,8 @@ struct HipSweep {
   // a sweep split into d_range calls gives the same depth/confidence however its earlier
   // pieces were requested (24 B/px per plane, <0.5% of a plane's time)
   int head_on(hipStream_t s, const UnetIO& io, int d) {
-    return check(launch_head_wta(ca.params, g, io, ws, a->depth_values, d, a->cost_out, true, s), "sweep: head/wta");
+    return check(launch_head_wta(ca.params, g, io, ws, a->depth_values, d, a->cost_out, true, s, refine_state),
+                 "sweep: head/wta");
   }
 };
 
@@ -768,7 +770,24 @@ int aarmvs_sweep(const aarmvs_sweep_args* a, hipStream_t stream) {
 }
 
 int aarmvs_sweep_p(const aarmvs_sweep_args* a, int precision, hipStream_t stream) {
+  return aarmvs_sweep_r(a, precision, nullptr, stream);
+}
+
+size_t aarmvs_refine_state_bytes(int B, int HW) {
+  if (B < 1 || HW < 1) return 0;
+  return (size_t)16 * B * HW;
+}
+
+int aarmvs_sweep_r(const aarmvs_sweep_args* a, int precision, const aarmvs_refine_args* refine,
+                   hipStream_t stream) {
   if (!a) return fail(AARMVS_ERR_INVALID, "sweep: null args");
+  if (refine && !refine->state)
+    return fail(AARMVS_ERR_INVALID, "sweep: aarmvs_refine_args without a state buffer "
+                                    "(aarmvs_refine_state_bytes(B, H * W) bytes of device memory)");
+  if (refine && a->record)
+    return fail(AARMVS_ERR_INVALID,
+                "sweep: the sub-plane refinement is an inference output; a recorded (training) sweep "
+                "takes no aarmvs_refine_args (aarmvs_refine_from_cost works on its cost volume)");
   if (precision != AARMVS_PREC_SPLIT && precision != AARMVS_PREC_FP16)
     return fail(AARMVS_ERR_INVALID, "sweep: unknown precision " + std::to_string(precision) +
                                         " (AARMVS_PREC_SPLIT = 0, AARMVS_PREC_FP16 = 1)");
@@ -835,6 +854,7 @@ int aarmvs_sweep_p(const aarmvs_sweep_args* a, int precision, hipStream_t stream
   }
   HipSweep run{a, T, g, ws, ca, evs.ev, {}};
   run.precision = precision;
+  run.refine_state = refine ? refine->state : nullptr;
   for (int i = 0; i < kSweepSlots; ++i) {
     const SweepStream id = plan.slot[i];
     if (id == kCaller) run.st[i] = stream;
@@ -884,6 +904,14 @@ int aarmvs_sweep_p(const aarmvs_sweep_args* a, int precision, hipStream_t stream
   if ((a->depth_out || a->conf_out) && a->d_end == a->D) {
     if ((e = launch_finalize(g, ws, a->depth_out, a->conf_out, stream)) != hipSuccess)
       return hip_fail(e, "sweep: finalize");
+  }
+  // the refined outputs describe the planes [0, d_end) of every call (a pixel whose winner is
+  // the call's last plane is unrefined until the next call has seen the plane after it)
+  if (refine && (refine->depth_refined_out || refine->conf_window_out || refine->index_out)) {
+    if ((e = launch_refine_finalize(ws.max_prob, ws.exp_sum, ws.depth, refine->state, a->depth_values,
+                                    a->B, a->D, a->d_end, a->H * a->W, refine->depth_refined_out,
+                                    refine->conf_window_out, refine->index_out, stream)) != hipSuccess)
+      return hip_fail(e, "sweep: refine finalize");
   }
   return AARMVS_OK;
 }
@@ -1011,6 +1039,38 @@ int aarmvs_wta_update(const float* cost, const float* depth_d, float* max_prob, 
     return fail(AARMVS_ERR_INVALID, "wta_update: bad arguments");
   hipError_t e = launch_wta_update(cost, depth_d, max_prob, depth_map, exp_sum, B, HW, stream);
   return e == hipSuccess ? AARMVS_OK : hip_fail(e, "wta_update");
+}
+
+int aarmvs_wta_refine_update(const float* cost, int d, float* max_prob, float* depth_map,
+                             float* exp_sum, void* state, const float* depth_d, int B, int HW,
+                             hipStream_t stream) {
+  if (!cost || !depth_d || !max_prob || !depth_map || !exp_sum || !state || B < 1 || HW < 1 || d < 0)
+    return fail(AARMVS_ERR_INVALID, "wta_refine_update: bad arguments");
+  hipError_t e = launch_wta_refine_update(cost, depth_d, d, max_prob, depth_map, exp_sum, state, B, HW, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "wta_refine_update");
+}
+
+int aarmvs_wta_refine_finalize(const float* max_prob, const float* depth_map, const float* exp_sum,
+                               const void* state, const float* depth_values, int B, int D, int n,
+                               int HW, float* depth_refined, float* conf_window, int* index,
+                               hipStream_t stream) {
+  if (!max_prob || !depth_map || !exp_sum || !state || !depth_values)
+    return fail(AARMVS_ERR_INVALID, "wta_refine_finalize: null pointer argument");
+  if (B < 1 || HW < 1 || D < 1 || n < 1 || n > D)
+    return fail(AARMVS_ERR_INVALID, "wta_refine_finalize: need B, HW >= 1 and 1 <= n <= D");
+  hipError_t e = launch_refine_finalize(max_prob, exp_sum, depth_map, state, depth_values, B, D, n, HW,
+                                        depth_refined, conf_window, index, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "wta_refine_finalize");
+}
+
+int aarmvs_refine_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
+                            float* depth_refined, float* conf_window, int* index, hipStream_t stream) {
+  if (!cost || !depth_values)
+    return fail(AARMVS_ERR_INVALID, "refine_from_cost: null pointer argument");
+  if (B < 1 || D < 1 || HW < 1)
+    return fail(AARMVS_ERR_INVALID, "refine_from_cost: need B, D, HW >= 1");
+  hipError_t e = launch_refine_from_cost(cost, depth_values, B, D, HW, depth_refined, conf_window, index, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "refine_from_cost");
 }
 
 int aarmvs_unet_step(const float* x, int B, int H, int W, int nsrc, int step,

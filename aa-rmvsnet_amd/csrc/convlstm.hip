@@ -1312,6 +1312,66 @@ __device__ __forceinline__ void wta_select(float cost, float dv, float& max_prob
   exp_sum = __fadd_rn(exp_sum, pr);
 }
 
+// ---------------------------------------------------------------------------
+// Sub-plane refinement of the winner-take-all (opt-in, beyond the reference).
+// Per pixel, beside the WTA images: the winner's plane index and the probabilities of the planes
+// next to it, kept online (16 B per pixel in a caller-owned buffer).  The head kernel, the
+// standalone per-plane pair and the from-the-volume kernel all go through refine_step /
+// refine_finish, so they agree bit for bit on the same cost values.
+// ---------------------------------------------------------------------------
+struct RefineState {
+  int idx;                       // the winner's plane, -1 while no plane has won
+  float p_prev, p_left, p_right; // p of the last plane seen; p of the planes idx - 1 and idx + 1
+};
+static_assert(sizeof(RefineState) == 16, "aarmvs_refine_state_bytes is 16 B per pixel");
+
+__device__ __forceinline__ RefineState refine_load(const void* state, size_t q) {
+  const int4 v = reinterpret_cast<const int4*>(state)[q];
+  return {v.x, __int_as_float(v.y), __int_as_float(v.z), __int_as_float(v.w)};
+}
+__device__ __forceinline__ void refine_store(void* state, size_t q, const RefineState& r) {
+  reinterpret_cast<int4*>(state)[q] =
+      make_int4(r.idx, __float_as_int(r.p_prev), __float_as_int(r.p_left), __float_as_int(r.p_right));
+}
+
+// plane d's update, from the plane's cost and max_prob BEFORE wta_select: p and the flag are
+// the values wta_select forms (expf of the same cost, the strict <)
+__device__ __forceinline__ void refine_step(float cost, int d, float max_prob_before, RefineState& r) {
+  const float p = expf(cost);
+  if (max_prob_before < p) {
+    r.idx = d;
+    r.p_left = r.p_prev;
+    r.p_right = 0.0f;
+  } else if (r.idx == d - 1) {
+    r.p_right = p;
+  }
+  r.p_prev = p;
+}
+
+// the three outputs of one pixel after n planes; dv: the batch element's depth_values [D];
+// max_prob / exp_sum / depth: the WTA images' values (max_prob is p of the winner)
+__device__ __forceinline__ void refine_finish(const RefineState& r, float max_prob, float exp_sum,
+                                              float depth, const float* __restrict__ dv, int n,
+                                              float& depth_refined, float& conf_window) {
+#pragma clang fp contract(off)
+  const int w = r.idx;
+  depth_refined = depth;
+  if (w < 0) {
+    conf_window = __fdiv_rn(max_prob, exp_sum);
+    return;
+  }
+  const bool left = w >= 1, right = w + 1 < n;
+  const float pl = left ? r.p_left : 0.0f, pr = right ? r.p_right : 0.0f;
+  const float s = __fadd_rn(__fadd_rn(pl, max_prob), pr);
+  conf_window = __fdiv_rn(s, exp_sum);
+  if (left && right) {
+    const float dw = dv[w];
+    const float num = __fadd_rn(__fmul_rn(pl, __fsub_rn(dv[w - 1], dw)),
+                                __fmul_rn(pr, __fsub_rn(dv[w + 1], dw)));
+    if (isfinite(s) && isfinite(num)) depth_refined = __fadd_rn(dw, __fdiv_rn(num, s));
+  }
+}
+
 // aarmvs_wta_update: the online WTA of one plane on a caller-given cost slice [B,HW]
 __global__ void __launch_bounds__(256) wta_update_kernel(const float* __restrict__ cost,
                                                          const float* __restrict__ depth_d,
@@ -1343,6 +1403,9 @@ hipError_t launch_wta_update(const float* cost, const float* depth_d, float* max
 // taps are 18 ds_read_b128 (the fma order stays channel-major, tap-minor), the staging 2 16-B
 // stores per pixel (27.8 vs 28.8 us per plane at the headline against a channel-major tile
 // read by 72 scalar LDS loads; bit-identical).
+// REFINE: the sweep's refining variant also carries the sub-plane state (loaded with the WTA
+// state, stored with it); the default instantiation has no trace of it.
+template <bool REFINE>
 __global__ void __launch_bounds__(256) head_wta_kernel(const float* __restrict__ h4,
                                                         const float* __restrict__ w,
                                                         const float* __restrict__ bias, int H,
@@ -1352,7 +1415,7 @@ __global__ void __launch_bounds__(256) head_wta_kernel(const float* __restrict__
                                                         float* __restrict__ exp_sum,
                                                         float* __restrict__ depth,
                                                         double* __restrict__ zero_stats,
-                                                        int zero_n) {
+                                                        int zero_n, void* __restrict__ refine) {
 #pragma clang fp contract(off)
   constexpr int TW2 = kHeadTW + 2, NPX = (kHeadTH + 2) * TW2;
   __shared__ float4 t[NPX][2];
@@ -1374,6 +1437,10 @@ __global__ void __launch_bounds__(256) head_wta_kernel(const float* __restrict__
     mp = max_prob[q];
     dp = depth[q];
     es = exp_sum[q];
+  }
+  RefineState rs{-1, 0.f, 0.f, 0.f};   // plane 0 starts from the reset state
+  if constexpr (REFINE) {
+    if (wta && own && d > 0) rs = refine_load(refine, q);
   }
   for (int rem = threadIdx.x; rem < NPX; rem += 256) {
     const int yy = y0 - 1 + rem / TW2, xx = x0 - 1 + rem % TW2;
@@ -1404,10 +1471,12 @@ __global__ void __launch_bounds__(256) head_wta_kernel(const float* __restrict__
   const float cost = acc + bias[0];
   if (cost_out) cost_out[((size_t)b * D + d) * HW + p] = cost;
   if (wta) {
+    if constexpr (REFINE) refine_step(cost, d, mp, rs);
     wta_select(cost, dvals[b * D + d], mp, dp, es);
     max_prob[q] = mp;
     depth[q] = dp;
     exp_sum[q] = es;
+    if constexpr (REFINE) refine_store(refine, q, rs);
   }
 }
 
@@ -1418,6 +1487,72 @@ __global__ void finalize_kernel(const float* __restrict__ max_prob, const float*
        i += (size_t)gridDim.x * blockDim.x) {
     if (depth_out) depth_out[i] = depth[i];
     if (conf_out) conf_out[i] = __fdiv_rn(max_prob[i], exp_sum[i]);
+  }
+}
+
+// the refining finalize: depth_refined / conf_window / index of B*HW pixels after n planes
+__global__ void __launch_bounds__(256) refine_finalize_kernel(
+    const float* __restrict__ max_prob, const float* __restrict__ exp_sum,
+    const float* __restrict__ depth, const void* __restrict__ state,
+    const float* __restrict__ dvals, int D, int n, int HW, float* __restrict__ depth_refined,
+    float* __restrict__ conf_window, int* __restrict__ index) {
+  const int b = blockIdx.y;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const size_t q = (size_t)b * HW + p;
+    const RefineState rs = refine_load(state, q);
+    float dr, cw;
+    refine_finish(rs, max_prob[q], exp_sum[q], depth[q], dvals + (size_t)b * D, n, dr, cw);
+    if (depth_refined) depth_refined[q] = dr;
+    if (conf_window) conf_window[q] = cw;
+    if (index) index[q] = rs.idx;
+  }
+}
+
+// aarmvs_wta_refine_update: aarmvs_wta_update of plane d plus the sub-plane state, on a
+// caller-given cost slice [B,HW]; d == 0 starts from the reset state
+__global__ void __launch_bounds__(256) wta_refine_update_kernel(
+    const float* __restrict__ cost, const float* __restrict__ depth_d, int d,
+    float* __restrict__ max_prob, float* __restrict__ depth, float* __restrict__ exp_sum,
+    void* __restrict__ state, int HW) {
+  const int b = blockIdx.y;
+  const float dv = depth_d[b];
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const size_t q = (size_t)b * HW + p;
+    float mp = max_prob[q], dp = depth[q], es = exp_sum[q];
+    RefineState rs{-1, 0.f, 0.f, 0.f};
+    if (d != 0) rs = refine_load(state, q);
+    const float c = cost[q];
+    refine_step(c, d, mp, rs);
+    wta_select(c, dv, mp, dp, es);
+    max_prob[q] = mp;
+    depth[q] = dp;
+    exp_sum[q] = es;
+    refine_store(state, q, rs);
+  }
+}
+
+// aarmvs_refine_from_cost: the same over a whole cost volume [B,D,HW], one thread per
+// (b, pixel), coalesced over pixels; the WTA images and the state stay in registers
+__global__ void __launch_bounds__(256) refine_from_cost_kernel(
+    const float* __restrict__ cost, const float* __restrict__ dvals, int D, int HW,
+    float* __restrict__ depth_refined, float* __restrict__ conf_window, int* __restrict__ index) {
+  const int b = blockIdx.y;
+  const float* dv = dvals + (size_t)b * D;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const float* c = cost + (size_t)b * D * HW + p;
+    float mp = 0.f, dp = 0.f, es = 0.f;
+    RefineState rs{-1, 0.f, 0.f, 0.f};
+    for (int d = 0; d < D; ++d) {
+      const float v = c[(size_t)d * HW];
+      refine_step(v, d, mp, rs);
+      wta_select(v, dv[d], mp, dp, es);
+    }
+    const size_t q = (size_t)b * HW + p;
+    float dr, cw;
+    refine_finish(rs, mp, es, dp, dv, D, dr, cw);
+    if (depth_refined) depth_refined[q] = dr;
+    if (conf_window) conf_window[q] = cw;
+    if (index) index[q] = rs.idx;
   }
 }
 
@@ -1714,15 +1849,16 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
 
 hipError_t launch_head_wta(const float* params, const SweepGeom& g, const UnetIO& io,
                            const Workspace& ws, const float* depth_values, int d,
-                           float* cost_out, bool wta, hipStream_t s) {
+                           float* cost_out, bool wta, hipStream_t s, void* refine_state) {
   const ParamLayout& L = param_layout();
   const int blocks = ((g.W + kHeadTW - 1) / kHeadTW) * ((g.H + kHeadTH - 1) / kHeadTH);
   ProfScope ps(s, K_HEAD_WTA);
-  hipLaunchKernelGGL(head_wta_kernel, dim3(blocks, g.B), dim3(256), 0, s, io.h_new[4],
+  auto kernel = refine_state ? head_wta_kernel<true> : head_wta_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(blocks, g.B), dim3(256), 0, s, io.h_new[4],
                      params + L.pk_off[P_HW], params + L.pk_off[P_HB], g.H, g.W, depth_values, d,
                      g.D, cost_out, wta ? 1 : 0, ws.max_prob, ws.exp_sum, ws.depth,
                      io.clear_stats ? io.reg_stats : nullptr,
-                     (int)(ws.reg_stats_bytes / sizeof(double)));
+                     (int)(ws.reg_stats_bytes / sizeof(double)), refine_state);
   return hipGetLastError();
 }
 
@@ -1733,6 +1869,37 @@ hipError_t launch_finalize(const SweepGeom& g, const Workspace& ws, float* depth
   ProfScope ps(s, K_FINALIZE);
   hipLaunchKernelGGL(finalize_kernel, dim3(blocks), dim3(256), 0, s, ws.max_prob, ws.exp_sum,
                      ws.depth, n, depth_out, conf_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_refine_finalize(const float* max_prob, const float* exp_sum, const float* depth,
+                                  const void* state, const float* depth_values, int B, int D, int n,
+                                  int HW, float* depth_refined, float* conf_window, int* index,
+                                  hipStream_t s) {
+  const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
+  ProfScope ps(s, K_REFINE);
+  hipLaunchKernelGGL(refine_finalize_kernel, dim3(blocks, B), dim3(256), 0, s, max_prob, exp_sum,
+                     depth, state, depth_values, D, n, HW, depth_refined, conf_window, index);
+  return hipGetLastError();
+}
+
+hipError_t launch_wta_refine_update(const float* cost, const float* depth_d, int d, float* max_prob,
+                                    float* depth, float* exp_sum, void* state, int B, int HW,
+                                    hipStream_t s) {
+  const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
+  ProfScope ps(s, K_HEAD_WTA);
+  hipLaunchKernelGGL(wta_refine_update_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_d, d,
+                     max_prob, depth, exp_sum, state, HW);
+  return hipGetLastError();
+}
+
+hipError_t launch_refine_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
+                                   float* depth_refined, float* conf_window, int* index,
+                                   hipStream_t s) {
+  const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
+  ProfScope ps(s, K_REFINE);
+  hipLaunchKernelGGL(refine_from_cost_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_values,
+                     D, HW, depth_refined, conf_window, index);
   return hipGetLastError();
 }
 

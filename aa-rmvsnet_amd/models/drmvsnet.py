@@ -6,7 +6,8 @@ Same public names, constructor/forward signatures, return values and submodule n
 keys load unchanged) as the reference:
 
 * ``EMVSNet(disparity_level, image_scale=0.25, max_h=960, max_w=480, return_depth=False)``
-  (drmvsnet.py:234-253) and ``forward(imgs, proj_matrices, depth_values)``
+  (drmvsnet.py:234-253; ``refine_depth=True`` with ``return_depth=True`` adds the sub-plane
+  ``depth_refined`` and ``photometric_confidence_window`` to the result, off by default) and ``forward(imgs, proj_matrices, depth_values)``
   (drmvsnet.py:255-345);
 * ``mvsnet_cls_loss`` (drmvsnet.py:347-381);
 * ``FeatNet``, ``IntraViewAAModule``, ``InterViewAAModule``, ``UNetConvLSTM`` and the
@@ -347,8 +348,15 @@ class EMVSNet(nn.Module):
                      "warp gather/scatter) on gfx950")
 
     def __init__(self, disparity_level, image_scale=0.25, max_h=960, max_w=480, return_depth=False,
-                 evidential=True, return_cost=False, checkpoint_planes=0, sweep_precision="split"):
+                 evidential=True, return_cost=False, checkpoint_planes=0, sweep_precision="split",
+                 refine_depth=False):
         super().__init__()
+        # sub-plane refinement of the WTA depth on the return_depth=True path (opt-in, beyond the
+        # reference; include/aarmvs.h, aarmvs_sweep_r): two more keys in the result dict
+        if refine_depth and not return_depth:
+            raise ValueError("EMVSNet: refine_depth needs return_depth=True (it refines the depth map of "
+                             "the inference sweep; aarmvs.ops.refine_from_cost works on a cost volume)")
+        self.refine_depth = bool(refine_depth)
         # precision of the regulariser's convs on the return_depth=True (inference) path only:
         # "split" (parity) or "fp16" (aarmvs.ops.DepthSweep); the other forwards, training
         # included, always run the split mode
@@ -443,12 +451,17 @@ class EMVSNet(nn.Module):
                 evidential, prob_combine = self.evidential(prob, depth_values)
             return prob, evidential, prob_combine
 
-        out = sweep(ref, srcs, ref_proj, src_projs, dv, want_depth=True, want_cost=evidential_on)
+        out = sweep(ref, srcs, ref_proj, src_projs, dv, want_depth=True, want_cost=evidential_on,
+                    want_refined=self.refine_depth)
         evidential = None
         if evidential_on:
             evidential, _ = self.evidential(_ops.softmax_depth(out["cost"]), depth_values)
-        return {"depth": out["depth"], "photometric_confidence": out["conf"],
-                "evidential_prediction": evidential}
+        res = {"depth": out["depth"], "photometric_confidence": out["conf"],
+               "evidential_prediction": evidential}
+        if self.refine_depth:
+            res["depth_refined"] = out["depth_refined"]
+            res["photometric_confidence_window"] = out["conf_window"]
+        return res
 
 
 def mvsnet_cls_loss(prob_volume, depth_gt, mask, depth_value, return_prob_map=False):

@@ -225,6 +225,41 @@ typedef enum aarmvs_precision {
  * aarmvs_sweep(a, s) is aarmvs_sweep_p(a, AARMVS_PREC_SPLIT, s).  The mode is a parameter of
  * the call, not a field of aarmvs_sweep_args, so the struct keeps its size. */
 int aarmvs_sweep_p(const aarmvs_sweep_args* args, int precision, hipStream_t stream);
+
+/* Sub-plane refinement of the sweep's winner-take-all (opt-in, inference only, beyond the
+ * reference: the reference keeps the winning plane's depth and max_prob / exp_sum).  Beside the
+ * WTA images the head kernel keeps, per pixel, the winner's plane index w (first maximum, the
+ * strict < of the WTA; -1 while no plane has won) and p = exp(cost) of the planes w - 1 and
+ * w + 1.  With n = the planes processed since plane 0, all in fp32 with every operation rounded
+ * on its own:
+ *   a pixel is refinable when 1 <= w and w + 1 < n (both neighbours seen); then
+ *     s   = (p[w-1] + p[w]) + p[w+1]
+ *     num = p[w-1] (d[w-1] - d[w]) + p[w+1] (d[w+1] - d[w])       d[.] = depth_values[b*D + .]
+ *     depth_refined = d[w] + num / s                   (any spacing of the depth values)
+ *   otherwise (winner on the first or the last plane seen, no winner), or when s or num is not
+ *   finite (exp overflow, a NaN cost), depth_refined is the WTA depth image's value, bit for bit;
+ *   conf_window = s' / exp_sum, s' = p[w] plus the neighbours that exist (one-sided at the
+ *   borders; max_prob / exp_sum with no winner), so conf_window >= the WTA confidence and is NaN
+ *   where that is; index = w (int32).
+ * state: aarmvs_refine_state_bytes(B, H*W) = 16 B per pixel of caller-owned device memory,
+ * 16-byte aligned, (int32 w, float p of the last plane, p[w-1], p[w+1]); plane 0 starts it afresh
+ * and it is complete, like the WTA images, only after contiguous calls from plane 0 through one
+ * workspace and one state buffer: a sweep split into d_range calls equals the whole sweep.  The
+ * outputs ([B,H,W] each, any may be NULL) are written at the end of EVERY call and describe the
+ * planes [0, d_end).  The sweep workspace and its layout are unchanged, depth_out / conf_out /
+ * cost_out are bit-identical with and without refinement, and the head kernel reads and writes
+ * 16 B per pixel and plane more (measured cost: DESIGN.md §8).
+ * aarmvs_sweep_r(a, p, NULL, s) is aarmvs_sweep_p(a, p, s).  Both precisions; a NULL state or a
+ * training record with refine != NULL: AARMVS_ERR_INVALID. */
+typedef struct aarmvs_refine_args {
+  void* state;               /* aarmvs_refine_state_bytes(B, H*W) bytes, required */
+  float* depth_refined_out;  /* [B,H,W] or NULL */
+  float* conf_window_out;    /* [B,H,W] or NULL */
+  int* index_out;            /* [B,H,W] int32 or NULL */
+} aarmvs_refine_args;
+size_t aarmvs_refine_state_bytes(int B, int HW);   /* 16 * B * HW; 0 for B, HW < 1 */
+int aarmvs_sweep_r(const aarmvs_sweep_args* args, int precision, const aarmvs_refine_args* refine,
+                   hipStream_t stream);
 /* A stream for aux_stream owned by the library (one per device, created on first use, never
  * destroyed): a process gets four hardware queues and streams beyond four share them, so a
  * caller without streams of its own passes this one rather than creating a fifth (the library's
@@ -331,6 +366,25 @@ int aarmvs_cost_slice(const float* ref_fea, const float* const* src_fea, const f
  * the confidence is max_prob / exp_sum after the last plane (:339). */
 int aarmvs_wta_update(const float* cost, const float* depth_d, float* max_prob, float* depth_map,
                       float* exp_sum, int B, int HW, hipStream_t stream);
+
+/* The refining form of the above, for cost planes that do not come from a sweep (see
+ * aarmvs_sweep_r for the definition): aarmvs_wta_refine_update is aarmvs_wta_update of plane d
+ * (the planes must come in order, d = 0, 1, ...) that also maintains `state`
+ * (aarmvs_refine_state_bytes(B, HW) bytes; d == 0 resets it -- the WTA images are the caller's to
+ * zero); aarmvs_wta_refine_finalize writes depth_refined / conf_window [B,HW] float and index
+ * [B,HW] int32 (each may be NULL) after n planes from the images, the state and depth_values
+ * [B,D], 1 <= n <= D.  aarmvs_refine_from_cost gives the same three outputs (and n = D) from a
+ * whole cost volume [B,D,HW], e.g. a training sweep's: the same expressions in the same order, so
+ * it equals the online result bit for bit on the same cost values. */
+int aarmvs_wta_refine_update(const float* cost, int d, float* max_prob, float* depth_map,
+                             float* exp_sum, void* state, const float* depth_d, int B, int HW,
+                             hipStream_t stream);
+int aarmvs_wta_refine_finalize(const float* max_prob, const float* depth_map, const float* exp_sum,
+                               const void* state, const float* depth_values, int B, int D, int n,
+                               int HW, float* depth_refined, float* conf_window, int* index,
+                               hipStream_t stream);
+int aarmvs_refine_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
+                            float* depth_refined, float* conf_window, int* index, hipStream_t stream);
 
 /* softmax over the depth axis of cost [B,D,H,W] (drmvsnet.py:291/:342). */
 int aarmvs_softmax_depth(const float* cost, float* prob, int B, int D, int HW,

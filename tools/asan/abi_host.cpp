@@ -138,6 +138,23 @@ int main() {
                           nullptr, nullptr) == AARMVS_ERR_INVALID);
   CHECK(aarmvs_wta_update(dummy, dummy, dummy, dummy, nullptr, 1, 64, nullptr) == AARMVS_ERR_INVALID);
   CHECK(aarmvs_wta_update(dummy, dummy, dummy, dummy, dummy, 1, 0, nullptr) == AARMVS_ERR_INVALID);
+  // the sub-plane refinement's entries: sizes, and rejections before any device work
+  CHECK(aarmvs_refine_state_bytes(2, 720) == 23040);
+  CHECK(aarmvs_refine_state_bytes(0, 720) == 0 && aarmvs_refine_state_bytes(2, 0) == 0);
+  aarmvs_refine_args rf;
+  std::memset(&rf, 0, sizeof(rf));
+  CHECK(aarmvs_sweep_r(&a, AARMVS_PREC_SPLIT, &rf, nullptr) == AARMVS_ERR_INVALID);   // state null
+  CHECK(aarmvs_sweep_r(nullptr, AARMVS_PREC_SPLIT, &rf, nullptr) == AARMVS_ERR_INVALID);
+  CHECK(aarmvs_wta_refine_update(dummy, 0, dummy, dummy, dummy, nullptr, dummy, 1, 64, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_wta_refine_update(dummy, -1, dummy, dummy, dummy, dummy, dummy, 1, 64, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_wta_refine_finalize(dummy, dummy, dummy, dummy, dummy, 1, 4, 5, 64, dummy, dummy, nullptr,
+                                   nullptr) == AARMVS_ERR_INVALID);   // n > D
+  CHECK(aarmvs_wta_refine_finalize(dummy, dummy, dummy, nullptr, dummy, 1, 4, 4, 64, dummy, dummy, nullptr,
+                                   nullptr) == AARMVS_ERR_INVALID);
+  CHECK(aarmvs_refine_from_cost(dummy, nullptr, 1, 4, 64, dummy, dummy, nullptr, nullptr) == AARMVS_ERR_INVALID);
+  CHECK(aarmvs_refine_from_cost(dummy, dummy, 1, 0, 64, dummy, dummy, nullptr, nullptr) == AARMVS_ERR_INVALID);
   CHECK(aarmvs_unet_step(dummy, 1, 8, 8, 1, -1, dummy, dummy, dummy, nullptr) == AARMVS_ERR_INVALID);
   CHECK(aarmvs_unet_step(dummy, 1, 8, 9, 1, 0, dummy, dummy, dummy, nullptr) == AARMVS_ERR_INVALID);
   CHECK(aarmvs_softmax_depth(dummy, dummy, 1, 0, 64, nullptr) == AARMVS_ERR_INVALID);
