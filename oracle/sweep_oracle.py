@@ -160,12 +160,14 @@ LOGIT_HOOK = None
 GATE_HOOK = None
 
 
-def cost_slice(ref_fea, src_feas, rels, depth, P, fast: bool = False) -> torch.Tensor:
-    """-(sum_v (1+w_v)(warp_v-ref)^2)/(N-1), drmvsnet.py:307-319 (sign folded in)."""
+def cost_slice(ref_fea, src_feas, rels, depth, P, fast: bool = False, stage_sq=None) -> torch.Tensor:
+    """-(sum_v (1+w_v)(warp_v-ref)^2)/(N-1), drmvsnet.py:307-319 (sign folded in).
+    ``stage_sq`` (tests): a function applied to sq where it enters the omega network (the
+    aggregation keeps the unstaged sq), to model an operand staging of the library's."""
     acc = None
     for src, rel in zip(src_feas, rels):
         sq = (homo_warp(src, rel, depth, fast) - ref_fea).pow(2)
-        w = omega_weight(sq, P, fast)
+        w = omega_weight(sq if stage_sq is None else stage_sq(sq), P, fast)
         term = (w + 1) * sq
         acc = term if acc is None else acc + term
     return -1 * (acc / len(src_feas))
@@ -218,33 +220,44 @@ def unet_step(x, state, P, fast=False):
 # ----------------------------------------------------------------------------------
 @torch.no_grad()
 def sweep(ref_fea, src_feas, ref_proj, src_projs, depth_values, P, planes=None,
-          want_volume=True, fast=False, plane_times=None):
+          want_volume=True, fast=False, plane_times=None, dtype=torch.float32, stage=None):
     """EMVSNet.forward's depth loop on precomputed features.
 
     Returns dict(depth [B,H,W], conf [B,H,W], cost [B,D,H,W] or None,
     prob [B,D,H,W] or None).  ``planes`` limits the loop (CPU-baseline sampling);
     ``fast`` warps with F.grid_sample (see homo_warp); ``plane_times``, if a list,
-    receives each plane's wall seconds.
+    receives each plane's wall seconds.  ``dtype`` (tests): torch.float64 runs the same
+    arithmetic in float64 on the reference's fp32 sampling grid (needs ``fast``: see
+    homo_warp).  ``stage`` (tests): {"x": f, "sq": g}, either optional; f is applied to each
+    plane's cost slice before the regulariser, g to sq where it enters the omega network
+    (cost_slice's ``stage_sq``): the two points where the library stages an operand at a
+    scale taken from the sweep's feature bound.
     """
     import time
-    P = {k: v.float() for k, v in P.items()}
+    if dtype != torch.float32 and not fast:
+        raise ValueError("sweep: dtype other than float32 needs fast=True (the explicit gather is fp32)")
+    stage = stage or {}
+    P = {k: v.to(dtype) for k, v in P.items()}
     B, C, H, W = ref_fea.shape
     rels = [relative_projection(sp, ref_proj) for sp in src_projs]
     D = depth_values.shape[1] if planes is None else planes
-    state = init_state(B, H, W)
-    depth_img = torch.zeros(B, H, W)
-    max_prob = torch.zeros(B, H, W)
-    exp_sum = torch.zeros(B, H, W)
+    state = [(h.to(dtype), c.to(dtype)) for h, c in init_state(B, H, W)]
+    depth_img = torch.zeros(B, H, W, dtype=dtype)
+    max_prob = torch.zeros(B, H, W, dtype=dtype)
+    exp_sum = torch.zeros(B, H, W, dtype=dtype)
     costs = []
     for d in range(D):
         t0 = time.perf_counter()
         dv = depth_values[:, d].float()
-        x = cost_slice(ref_fea.float(), [s.float() for s in src_feas], rels, dv, P, fast)
+        x = cost_slice(ref_fea.to(dtype), [s.to(dtype) for s in src_feas], rels, dv, P, fast,
+                       stage.get("sq"))
+        if stage.get("x") is not None:
+            x = stage["x"](x)
         cost, state = unet_step(x, state, P, fast)
         if want_volume:
             costs.append(cost)
         prob = torch.exp(cost.squeeze(1))                       # :324 (no max-subtraction)
-        flag = (max_prob < prob).float()                        # :327 strict: first plane wins ties
+        flag = (max_prob < prob).to(dtype)                      # :327 strict: first plane wins ties
         max_prob = flag * prob + (1 - flag) * max_prob          # :328 arithmetic select (NaN-faithful)
         depth_img = flag * dv.view(B, 1, 1).expand(B, H, W) + (1 - flag) * depth_img
         exp_sum = exp_sum + prob                                # :334
