@@ -51,6 +51,18 @@ class RefineArgs(ctypes.Structure):
                 ("index_out", c_void_p)]
 
 
+class PosteriorArgs(ctypes.Structure):
+    """Mirror of ``aarmvs_posterior_args``."""
+    _fields_ = [("state", c_void_p), ("mean_out", c_void_p), ("std_out", c_void_p),
+                ("entropy_out", c_void_p), ("runner_up_out", c_void_p)]
+
+
+class SweepOptions(ctypes.Structure):
+    """Mirror of ``aarmvs_sweep_options``; ``size`` is ``ctypes.sizeof(SweepOptions)``."""
+    _fields_ = [("size", c_size_t), ("precision", c_int), ("refine", ctypes.POINTER(RefineArgs)),
+                ("posterior", ctypes.POINTER(PosteriorArgs))]
+
+
 class BackwardArgs(ctypes.Structure):
     """Mirror of ``aarmvs_backward_args``."""
     _fields_ = [
@@ -129,6 +141,8 @@ SIGNATURES = {
     "aarmvs_sweep_p": (c_int, [ctypes.POINTER(SweepArgs), c_int, c_void_p]),
     "aarmvs_refine_state_bytes": (c_size_t, [c_int, c_int]),
     "aarmvs_sweep_r": (c_int, [ctypes.POINTER(SweepArgs), c_int, ctypes.POINTER(RefineArgs), c_void_p]),
+    "aarmvs_posterior_state_bytes": (c_size_t, [c_int, c_int]),
+    "aarmvs_sweep_ex": (c_int, [ctypes.POINTER(SweepArgs), ctypes.POINTER(SweepOptions), c_void_p]),
     "aarmvs_aux_stream": (c_int, [ctypes.POINTER(c_void_p)]),
     "aarmvs_train_record_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "aarmvs_train_segment_bytes": (c_int, [c_int] * 5 + [ctypes.POINTER(c_size_t)] * 2),
@@ -158,6 +172,9 @@ SIGNATURES = {
     "aarmvs_wta_refine_update": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),
     "aarmvs_wta_refine_finalize": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 4),
     "aarmvs_refine_from_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 4),
+    "aarmvs_wta_posterior_update": (c_int, [c_void_p, c_int] + [c_void_p] * 5 + [c_int, c_int, c_void_p]),
+    "aarmvs_wta_posterior_finalize": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5),
+    "aarmvs_posterior_from_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
     "aarmvs_fusion_filter": (c_int, [ctypes.POINTER(FusionArgs), c_void_p]),
     "aarmvs_pyr_down": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "aarmvs_fusion_points_workspace_bytes": (c_size_t, [c_int, c_int]),

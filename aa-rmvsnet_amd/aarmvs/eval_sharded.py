@@ -16,6 +16,9 @@ Outputs per sample, as eval.py names them (``filename.format(kind, ext)``):
   depth_refined_0/, confidence_window_0/  with --refine_depth (not in eval.py): the sweep's
                             sub-plane depth and windowed confidence (include/aarmvs.h,
                             aarmvs_sweep_r), always the sweep's, also where the head runs
+  depth_mean_0/, depth_std_0/, entropy_0/, runner_up_0/  with --posterior_stats (not in
+                            eval.py): the sweep's depth-posterior statistics (include/aarmvs.h,
+                            aarmvs_posterior_args), at any D, also where the head runs
 eval.py's PNG previews are not written (data_io.save_png is broken on numpy >= 1.24,
 SURVEY §8f-4).
 
@@ -60,6 +63,9 @@ def parse_args(argv=None):
     ap.add_argument("--sweep_precision", choices=("split", "fp16"), default="split")
     # not in eval.py: also write the sub-plane refined depth and the windowed confidence
     ap.add_argument("--refine_depth", action="store_true")
+    # not in eval.py: also write the depth posterior's mean, standard deviation, entropy and
+    # runner-up probability
+    ap.add_argument("--posterior_stats", action="store_true")
     return ap.parse_args(argv)
 
 
@@ -101,7 +107,8 @@ def save_depth(args, rank: int = 0, world: int = 1, device=None, model=None) -> 
         model = EMVSNet(disparity_level=32, image_scale=args.image_scale, max_h=args.max_h,
                         max_w=args.max_w, return_depth=True,
                         sweep_precision=getattr(args, "sweep_precision", "split"),
-                        refine_depth=getattr(args, "refine_depth", False))
+                        refine_depth=getattr(args, "refine_depth", False),
+                        posterior_stats=getattr(args, "posterior_stats", False))
         if args.loadckpt:
             load_checkpoint(model, args.loadckpt)
     model = model.to(device).eval()
@@ -121,6 +128,11 @@ def save_depth(args, rank: int = 0, world: int = 1, device=None, model=None) -> 
                     raise ValueError("eval_sharded: --refine_depth needs a model built with refine_depth=True")
                 refined = {"depth_refined": out["depth_refined"].cpu().numpy(),
                            "confidence_window": out["photometric_confidence_window"].cpu().numpy()}
+            if getattr(args, "posterior_stats", False):
+                if "depth_mean" not in out:
+                    raise ValueError("eval_sharded: --posterior_stats needs a model built with posterior_stats=True")
+                refined = dict(refined or {})
+                refined.update({k: out[k].cpu().numpy() for k in ("depth_mean", "depth_std", "entropy", "runner_up")})
             for b, filename in enumerate(sample["filename"]):
                 path = lambda kind: os.path.join(save_dir, filename.format(kind + "_0", ".pfm"))
                 for kind in (("depth_est", "confidence") + (("epistemic", "aleatoric") if ev is not None else ())

@@ -564,6 +564,85 @@ def refine_from_cost(cost: torch.Tensor, depth_values: torch.Tensor) -> dict:
     return out
 
 
+POSTERIOR_KEYS = ("depth_mean", "depth_std", "entropy", "runner_up")
+
+
+def posterior_state(B: int, HW: int, device) -> torch.Tensor:
+    """A state buffer of the depth-posterior statistics (aarmvs_posterior_state_bytes: 16 B per
+    pixel)."""
+    n = lib().aarmvs_posterior_state_bytes(B, HW)
+    if n == 0:
+        raise AarmvsError(f"aarmvs: posterior state geometry B={B} HW={HW}")
+    return torch.empty(n // 4, dtype=torch.float32, device=device)
+
+
+def _check_posterior_state(state: torch.Tensor, B: int, HW: int, device) -> None:
+    if (not torch.is_tensor(state) or not state.is_cuda or state.device != device or not state.is_contiguous()
+            or state.numel() * state.element_size() < lib().aarmvs_posterior_state_bytes(B, HW)):
+        raise AarmvsError(f"aarmvs: the posterior state must be a contiguous tensor of {16 * B * HW} B on "
+                          f"{device} (ops.posterior_state(B, HW, device))")
+
+
+@_on_tensor_device
+def wta_posterior_update(cost: torch.Tensor, d: int, depth_d: torch.Tensor, max_prob: torch.Tensor,
+                         depth_map: torch.Tensor, exp_sum: torch.Tensor, state: torch.Tensor) -> None:
+    """``wta_update`` of plane ``d`` (planes in order from 0) that also keeps the posterior
+    statistics' ``state`` (``posterior_state(B, H*W, device)``; d == 0 resets it), in place
+    (aarmvs_wta_posterior_update)."""
+    ts = (cost, max_prob, depth_map, exp_sum)
+    _require_device(*ts)
+    B = cost.shape[0]
+    for t in ts:
+        if t.shape != cost.shape or not t.is_contiguous() or t.device != cost.device:
+            raise AarmvsError("aarmvs: wta_posterior_update needs contiguous tensors of one [B,H,W] shape")
+    HW = cost[0].numel()
+    _check_posterior_state(state, B, HW, cost.device)
+    dep = depth_d.reshape(-1).to(cost.device, torch.float32).contiguous()
+    if dep.numel() != B:
+        raise AarmvsError(f"aarmvs: depth_d must hold B={B} values")
+    if int(d) < 0:
+        raise AarmvsError(f"aarmvs: plane index {d} < 0")
+    check(lib().aarmvs_wta_posterior_update(cost.data_ptr(), int(d), max_prob.data_ptr(), depth_map.data_ptr(),
+                                            exp_sum.data_ptr(), state.data_ptr(), dep.data_ptr(), B, HW,
+                                            _stream()), "wta_posterior_update")
+
+
+@_on_tensor_device
+def wta_posterior_finalize(exp_sum: torch.Tensor, state: torch.Tensor) -> dict:
+    """{'depth_mean', 'depth_std', 'entropy', 'runner_up'}, each shaped like ``exp_sum`` [B,H,W],
+    of the planes given to ``wta_posterior_update`` so far (aarmvs_wta_posterior_finalize)."""
+    _require_device(exp_sum)
+    if exp_sum.dim() < 2 or not exp_sum.is_contiguous() or exp_sum.dtype != torch.float32:
+        raise AarmvsError("aarmvs: wta_posterior_finalize needs a contiguous float32 [B,H,W] exp_sum")
+    B, HW = exp_sum.shape[0], exp_sum[0].numel()
+    _check_posterior_state(state, B, HW, exp_sum.device)
+    out = {k: torch.empty_like(exp_sum) for k in POSTERIOR_KEYS}
+    check(lib().aarmvs_wta_posterior_finalize(exp_sum.data_ptr(), state.data_ptr(), B, HW,
+                                              *[out[k].data_ptr() for k in POSTERIOR_KEYS], _stream()),
+          "wta_posterior_finalize")
+    return out
+
+
+@_on_tensor_device
+def posterior_from_cost(cost: torch.Tensor, depth_values: torch.Tensor) -> dict:
+    """The depth-posterior statistics from a whole cost volume [B,D,H,W] and depth_values [B,D]
+    (aarmvs_posterior_from_cost): {'depth_mean', 'depth_std', 'entropy', 'runner_up'} [B,H,W]
+    float32, bit for bit what a sweep with ``want_posterior`` gives on the same cost values."""
+    _require_device(cost)
+    c = cost.detach().contiguous()
+    if c.dim() != 4 or c.dtype != torch.float32:
+        raise AarmvsError(f"aarmvs: posterior_from_cost cost must be float32 [B,D,H,W], got {tuple(c.shape)}")
+    B, D, H, W = c.shape
+    if tuple(depth_values.shape) != (B, D):
+        raise AarmvsError(f"aarmvs: depth_values must be [B={B},D={D}], got {tuple(depth_values.shape)}")
+    dv = depth_values.detach().to(c.device, torch.float32).contiguous()
+    out = {k: torch.empty(B, H, W, device=c.device) for k in POSTERIOR_KEYS}
+    check(lib().aarmvs_posterior_from_cost(c.data_ptr(), dv.data_ptr(), B, D, H * W,
+                                           *[out[k].data_ptr() for k in POSTERIOR_KEYS], _stream()),
+          "posterior_from_cost")
+    return out
+
+
 def aux_stream(device) -> torch.cuda.ExternalStream:
     """The library's aux stream of ``device`` (aarmvs_aux_stream): one per device, shared by every
     DepthSweep.  The process gets four hardware queues and streams beyond four share them (a
@@ -600,6 +679,7 @@ class DepthSweep:
         self.packed = pack_params(params, self.device)
         self._ws = {}
         self._refine = {}
+        self._posterior = {}
         self._aux = None
         self.overlap = overlap
 
@@ -646,6 +726,16 @@ class DepthSweep:
         if st is None:
             st = refine_state(B, H * W, self.device)
             self._refine = {key: st}
+        return st
+
+    def posterior_state(self, B, H, W) -> torch.Tensor:
+        """The posterior statistics' state of a (B, H, W) sweep (16 B per pixel), cached beside
+        the workspace, one geometry at a time: d_range calls with ``want_posterior`` continue it."""
+        key = (B, H, W)
+        st = self._posterior.get(key)
+        if st is None:
+            st = posterior_state(B, H * W, self.device)
+            self._posterior = {key: st}
         return st
 
     def relative(self, ref_proj, src_projs, B: int) -> torch.Tensor:
@@ -744,7 +834,7 @@ class DepthSweep:
     @_on_tensor_device
     def __call__(self, ref_fea, src_feas, ref_proj, src_projs, depth_values, *,
                  want_depth=True, want_cost=False, d_range=None, debug=False, cost_out=None,
-                 rel=None, record=None, record_d0=0, want_refined=False):
+                 rel=None, record=None, record_d0=0, want_refined=False, want_posterior=False):
         """Returns dict(depth, conf, cost, slice, omega) (entries None when not requested).
 
         ``want_refined`` (opt-in, inference only) adds ``depth_refined`` and ``conf_window``
@@ -753,6 +843,12 @@ class DepthSweep:
         plane (include/aarmvs.h, aarmvs_sweep_r).  They describe the planes up to the call's
         last one; with ``d_range`` every call of the sweep must pass ``want_refined``, which
         carries the state in ``self.refine_state(B, H, W)``.  The other outputs do not change.
+
+        ``want_posterior`` (opt-in, inference only, combinable with ``want_refined``) adds
+        ``depth_mean``, ``depth_std``, ``entropy`` (nats) and ``runner_up`` [B,H,W]: the moments of
+        the softmax over the planes' costs, its entropy and its second largest probability
+        (include/aarmvs.h, aarmvs_posterior_args), NaN exactly where ``conf`` is NaN or the sum
+        overflowed.  Same rules as ``want_refined``; the state is ``self.posterior_state(B, H, W)``.
 
         ``d_range=(d0, d1)`` runs planes d0..d1-1 only (d0 == 0 resets the hidden state;
         later ranges continue from the state the previous call left in the workspace).
@@ -835,6 +931,16 @@ class DepthSweep:
             refine.depth_refined_out = out["depth_refined"].data_ptr()
             refine.conf_window_out = out["conf_window"].data_ptr()
             refine.index_out = out["index"].data_ptr()
+        posterior = None
+        if want_posterior:
+            if record is not None:
+                raise AarmvsError("aarmvs: want_posterior is an inference output; a recorded (training) sweep "
+                                  "has none (ops.posterior_from_cost works on its cost volume)")
+            posterior = _lib.PosteriorArgs()
+            posterior.state = self.posterior_state(B, H, W).data_ptr()
+            for k, f in zip(POSTERIOR_KEYS, ("mean_out", "std_out", "entropy_out", "runner_up_out")):
+                out[k] = torch.empty(B, H, W, device=ref.device)
+                setattr(posterior, f, out[k].data_ptr())
         if record is not None:
             if self._precision != "split":
                 raise AarmvsError(f"aarmvs: precision {self._precision!r} is an inference mode; a recorded "
@@ -842,8 +948,14 @@ class DepthSweep:
             rec_struct = self._segment_struct(a, record, record_d0, d0, d1, ref.device)
         elif record_d0:
             raise AarmvsError("aarmvs: record_d0 without a record")
-        check(lib().aarmvs_sweep_r(ctypes.byref(a), self.PRECISIONS[self._precision],
-                                   ctypes.byref(refine) if refine is not None else None, _stream()), "sweep")
+        opts = _lib.SweepOptions()
+        opts.size = ctypes.sizeof(opts)
+        opts.precision = self.PRECISIONS[self._precision]
+        if refine is not None:
+            opts.refine = ctypes.pointer(refine)
+        if posterior is not None:
+            opts.posterior = ctypes.pointer(posterior)
+        check(lib().aarmvs_sweep_ex(ctypes.byref(a), ctypes.byref(opts), _stream()), "sweep")
         out["_keepalive"] = (rel, dv, srcs, ref, rec_struct)
         return out
 

@@ -22,7 +22,10 @@ DictAverageMeter does.  Each rank takes its contiguous shard of the test samples
 (``aarmvs.dist.shard_range``); the per-batch sums and batch counts are all-reduced, rank 0
 prints ``avg_test_scalars:``.  ``--refine_metrics`` adds the same six metrics of the sub-plane
 refined depth (``aarmvs.ops.refine_from_cost`` on the pass's cost volume; not in train.py) on a
-line of their own, ``avg_test_scalars_refined:``.  The evidential scalars, tensorboard summaries and the image /
+line of their own, ``avg_test_scalars_refined:``.  ``--uncertainty_metrics`` adds, on the line
+``avg_test_scalars_uncertainty:``, the sparsification error (AUSE) of the depth map's absolute
+error ranked by 1 - confidence and by the depth posterior's standard deviation, entropy and
+runner-up probability (``aarmvs.ops.posterior_from_cost``; not in train.py).  The evidential scalars, tensorboard summaries and the image /
 .pt dumps of test_sample are not reproduced.
 
 usage: python -m torch.distributed.run --nproc-per-node 8 -m aarmvs.train_ddp \\
@@ -84,6 +87,9 @@ def parse_args(argv=None):
     ap.add_argument("--refine_metrics", action="store_true",
                     help="with --testpath: also report the depth metrics of the sub-plane refined depth "
                          "(the local expectation over the winning plane and its neighbours)")
+    ap.add_argument("--uncertainty_metrics", action="store_true",
+                    help="with --testpath: also report how well 1 - confidence and the depth posterior's "
+                         "standard deviation, entropy and runner-up probability rank the depth error (AUSE)")
     return ap.parse_args(argv)
 
 
@@ -110,9 +116,57 @@ def _loss_and_depth(out, s, fused: bool):
 REFINED = "refined_"   # prefix of --refine_metrics' keys in run_test_pass's result
 
 
-def run_test_pass(model, loader, device, fused: bool, rank: int = 0, log=print, refine: bool = False) -> dict:
+AUSE = "ause_"         # prefix of --uncertainty_metrics' keys in run_test_pass's result
+RANKINGS = ("conf", "depth_std", "entropy", "runner_up")
+AUSE_STEPS = 50
+
+
+def _ause(err: torch.Tensor, unc: torch.Tensor) -> torch.Tensor:
+    """AUSE of one image's valid pixels (1-D tensors): sort by uncertainty, descending and stable
+    (NaN counts as the most uncertain); for k = 0..49 drop the first floor(k n / 50) pixels and
+    average the error of the rest; the same ranked by the error itself (the oracle); the mean
+    difference of the two curves over the mean error.  0 for an image with no valid pixel or no
+    error."""
+    n = err.numel()
+    e = err.double()
+    if n == 0 or float(e.sum()) == 0.0:
+        return torch.zeros((), dtype=torch.float64, device=err.device)
+    u = unc.double()
+    u = torch.where(torch.isnan(u), torch.full_like(u, float("inf")), u)
+    drop = (torch.arange(AUSE_STEPS, device=err.device) * n) // AUSE_STEPS
+
+    def curve(rank):
+        s = e[torch.sort(rank, descending=True, stable=True).indices]
+        tail = torch.cat([s.flip(0).cumsum(0).flip(0), s.new_zeros(1)])   # tail[i] = sum s[i:]
+        return tail[drop] / (n - drop)
+
+    return (curve(u) - curve(e)).mean() / e.mean()
+
+
+def sparsification_errors(depth_est, depth_gt, mask, cost, depth_values) -> dict:
+    """{ranking: [B] float64 AUSE per image} of |depth_est - depth_gt| over mask > 0.5 under the
+    RANKINGS: 1 - max softmax probability, and ops.posterior_from_cost's depth_std, entropy and
+    runner_up of ``cost`` [B,D,H,W] (a log-probability volume serves as well: the statistics do
+    not see a per-pixel shift of every plane)."""
+    from . import ops
+    post = ops.posterior_from_cost(cost.float().contiguous(), depth_values.float())
+    unc = {"conf": 1.0 - torch.softmax(cost.float(), 1).amax(1), "depth_std": post["depth_std"],
+           "entropy": post["entropy"], "runner_up": post["runner_up"]}
+    err = (depth_est.float() - depth_gt.float()).abs()
+    out = {k: [] for k in RANKINGS}
+    for b in range(err.shape[0]):
+        valid = mask[b] > 0.5
+        for k in RANKINGS:
+            out[k].append(_ause(err[b][valid], unc[k][b][valid]))
+    return {k: torch.stack(v) for k, v in out.items()}
+
+
+def run_test_pass(model, loader, device, fused: bool, rank: int = 0, log=print, refine: bool = False,
+                  uncertainty: bool = False) -> dict:
     """train.py:259-285 on this rank's loader: per batch the loss and the masked metrics of its
-    depth map, summed over batches and ranks, divided by the batch count.  ``refine``: also the
+    depth map, summed over batches and ranks, divided by the batch count.  ``uncertainty``: also
+    the batch's mean AUSE per ranking (sparsification_errors), under AUSE-prefixed keys, from the
+    same cost volume as ``refine`` uses.  ``refine``: also the
     metrics of ops.refine_from_cost's depth, under REFINED-prefixed keys.  Its cost volume is the
     model's with --fused_loss and the log of the probability volume otherwise (the same per-pixel
     shift on every plane, which the refinement's quotient cancels)."""
@@ -121,6 +175,8 @@ def run_test_pass(model, loader, device, fused: bool, rank: int = 0, log=print, 
     base = len(keys)
     if refine:
         keys = keys + [REFINED + k for k in keys[1:]]
+    if uncertainty:
+        keys = keys + [AUSE + k for k in RANKINGS]
     sums, count = [0.0] * len(keys), 0
     model.eval()
     with torch.no_grad():
@@ -136,7 +192,11 @@ def run_test_pass(model, loader, device, fused: bool, rank: int = 0, log=print, 
                 r = ops.refine_from_cost(cost.float(), s["depth_values"].float())
                 mr = ops.depth_metrics(r["depth_refined"], s["depth"].float(), s["mask"].float(),
                                        TEST_THRESHOLDS)
-                cells += [mr[k[len(REFINED):]] for k in keys[base:]]
+                cells += [mr[k[len(REFINED):]] for k in keys[base:] if k.startswith(REFINED)]
+            if uncertainty:
+                cost = out[0] if getattr(model, "return_cost", False) else torch.log(out[0])
+                au = sparsification_errors(depth_est, s["depth"], s["mask"], cost, s["depth_values"])
+                cells += [au[k].mean() for k in RANKINGS]
             row = torch.stack(cells).tolist()
             sums = [a + b for a, b in zip(sums, row)]
             count += 1
@@ -148,7 +208,8 @@ def run_test_pass(model, loader, device, fused: bool, rank: int = 0, log=print, 
 def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
     """Runs train.py's epochs on this rank's shard; returns {'losses', 'checkpoints',
     'test_scalars' (one dict per epoch when --testpath is given, else empty)[,
-    'test_scalars_refined' likewise with --refine_metrics]}."""
+    'test_scalars_refined' likewise with --refine_metrics][, 'test_scalars_uncertainty' likewise
+    with --uncertainty_metrics]}."""
     from datasets import find_dataset_def
     from models import EMVSNet
     device = torch.device(device or f"cuda:{local_device_index(env()[1])}")
@@ -201,7 +262,7 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
         sched.step()
     if rank == 0:
         os.makedirs(args.logdir, exist_ok=True)
-    losses, ckpts, test_scalars, test_scalars_refined = [], [], [], []
+    losses, ckpts, test_scalars, test_scalars_refined, test_scalars_uncertainty = [], [], [], [], []
     for epoch in range(start_epoch, args.epochs):
         sampler.set_epoch(epoch)
         for step, sample in enumerate(loader):
@@ -231,8 +292,12 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
             # forward synchronises buffers across ranks
             core = model.module if isinstance(model, torch.nn.parallel.DistributedDataParallel) else model
             scalars = run_test_pass(core, test_loader, device, args.fused_loss, rank, log,
-                                    refine=getattr(args, "refine_metrics", False))
-            test_scalars.append({k: v for k, v in scalars.items() if not k.startswith(REFINED)})
+                                    refine=getattr(args, "refine_metrics", False),
+                                    uncertainty=getattr(args, "uncertainty_metrics", False))
+            test_scalars.append({k: v for k, v in scalars.items() if not k.startswith((REFINED, AUSE))})
+            ause = {k[len(AUSE):]: v for k, v in scalars.items() if k.startswith(AUSE)}
+            if ause:
+                test_scalars_uncertainty.append(ause)
             refined = {k[len(REFINED):]: v for k, v in scalars.items() if k.startswith(REFINED)}
             if refined:
                 test_scalars_refined.append(refined)
@@ -240,9 +305,13 @@ def train(args, rank: int = 0, world: int = 1, device=None, log=print) -> dict:
                 log("avg_test_scalars:", test_scalars[-1])
                 if refined:
                     log("avg_test_scalars_refined:", refined)
+                if ause:
+                    log("avg_test_scalars_uncertainty:", ause)
     out = {"losses": losses, "checkpoints": ckpts, "test_scalars": test_scalars}
     if test_scalars_refined:
         out["test_scalars_refined"] = test_scalars_refined
+    if test_scalars_uncertainty:
+        out["test_scalars_uncertainty"] = test_scalars_uncertainty
     return out
 
 

@@ -216,9 +216,11 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
                             int stages = kUnetAll, int precision = AARMVS_PREC_SPLIT);
 hipError_t launch_head_wta(const float* params, const SweepGeom& g, const UnetIO& io,
                            const Workspace& ws, const float* depth_values, int d,
-                           float* cost_out, bool wta, hipStream_t s, void* refine_state = nullptr);
+                           float* cost_out, bool wta, hipStream_t s, void* refine_state = nullptr,
+                           void* posterior_state = nullptr);
 // ^ refine_state: the sub-plane refinement's per-pixel state (16 B per pixel) or null; non-null
-// launches the refining instantiation of the head kernel
+// launches the refining instantiation of the head kernel.  posterior_state: likewise the
+// depth-posterior statistics' state (16 B per pixel), independent of the former
 hipError_t launch_wta_update(const float* cost, const float* depth_d, float* max_prob,
                              float* depth, float* exp_sum, int B, int HW, hipStream_t s);
 hipError_t launch_finalize(const SweepGeom& g, const Workspace& ws, float* depth_out,
@@ -237,6 +239,17 @@ hipError_t launch_wta_refine_update(const float* cost, const float* depth_d, int
 hipError_t launch_refine_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
                                    float* depth_refined, float* conf_window, int* index,
                                    hipStream_t s);
+// depth-posterior statistics of the WTA (mean, std, entropy, runner-up): the outputs from exp_sum
+// and the state, one plane's standalone update (d == 0 resets the state), the whole from a volume
+hipError_t launch_posterior_finalize(const float* exp_sum, const void* state, int B, int HW,
+                                     float* mean, float* sd, float* entropy, float* runner_up,
+                                     hipStream_t s);
+hipError_t launch_wta_posterior_update(const float* cost, const float* depth_d, int d, float* max_prob,
+                                       float* depth, float* exp_sum, void* state, int B, int HW,
+                                       hipStream_t s);
+hipError_t launch_posterior_from_cost(const float* cost, const float* depth_values, int B, int D,
+                                      int HW, float* mean, float* sd, float* entropy,
+                                      float* runner_up, hipStream_t s);
 // the evidential head's epilogue (evidential.hip): forward when g_head is null (ev [4][HW],
 // pc [D][HW]), else the backward from g_ev / g_pc (either may be null) into g_head
 hipError_t launch_evidential(const float* const head[3], const float* dv, int D, int HW, float* ev,
@@ -399,7 +412,8 @@ enum KernelId : int {
   // the fp16 mode's 1-product cells and deconvs (AARMVS_PREC_FP16), in the order of K_CELL0 ..
   K_CELL0_FP16, K_CELL1_FP16, K_CELL2_FP16, K_CELL3_FP16, K_CELL4_FP16,
   K_DECONV0_FP16, K_DECONV1_FP16,
-  K_REFINE,   // the sub-plane refinement's finalize and its from-the-volume kernel
+  K_REFINE,   // the sub-plane refinement's finalize and its from-the-volume kernel; the
+              // depth-posterior statistics' two are counted here too (the list of names is fixed)
   K_COUNT
 };
 extern bool g_prof_on;

@@ -683,6 +683,7 @@ struct HipSweep {
   hipStream_t st[kSweepSlots];
   int precision = AARMVS_PREC_SPLIT;   // aarmvs_precision of the regulariser's units
   void* refine_state = nullptr;        // aarmvs_refine_args.state: the head also keeps it
+  void* posterior_state = nullptr;     // aarmvs_posterior_args.state: likewise
   int rc = 0, io_d = -1;
   UnetIO io_{};
 
@@ -758,7 +759,8 @@ struct HipSweep {
   // a sweep split into d_range calls gives the same depth/confidence however its earlier
   // pieces were requested (24 B/px per plane, <0.5% of a plane's time)
   int head_on(hipStream_t s, const UnetIO& io, int d) {
-    return check(launch_head_wta(ca.params, g, io, ws, a->depth_values, d, a->cost_out, true, s, refine_state),
+    return check(launch_head_wta(ca.params, g, io, ws, a->depth_values, d, a->cost_out, true, s, refine_state,
+                                 posterior_state),
                  "sweep: head/wta");
   }
 };
@@ -773,14 +775,48 @@ int aarmvs_sweep_p(const aarmvs_sweep_args* a, int precision, hipStream_t stream
   return aarmvs_sweep_r(a, precision, nullptr, stream);
 }
 
+int aarmvs_sweep_r(const aarmvs_sweep_args* a, int precision, const aarmvs_refine_args* refine,
+                   hipStream_t stream) {
+  aarmvs_sweep_options o{};
+  o.size = sizeof(o);
+  o.precision = precision;
+  o.refine = refine;
+  return aarmvs_sweep_ex(a, &o, stream);
+}
+
+size_t aarmvs_posterior_state_bytes(int B, int HW) {
+  if (B < 1 || HW < 1) return 0;
+  return (size_t)16 * B * HW;
+}
+
 size_t aarmvs_refine_state_bytes(int B, int HW) {
   if (B < 1 || HW < 1) return 0;
   return (size_t)16 * B * HW;
 }
 
-int aarmvs_sweep_r(const aarmvs_sweep_args* a, int precision, const aarmvs_refine_args* refine,
-                   hipStream_t stream) {
+int aarmvs_sweep_ex(const aarmvs_sweep_args* a, const aarmvs_sweep_options* options,
+                    hipStream_t stream) {
   if (!a) return fail(AARMVS_ERR_INVALID, "sweep: null args");
+  // the caller's struct may be older (shorter) than the library's: fields beyond its size are zero
+  aarmvs_sweep_options o{};
+  if (options) {
+    if (options->size < AARMVS_SWEEP_OPTIONS_SIZE_V1 || options->size > sizeof(o))
+      return fail(AARMVS_ERR_INVALID,
+                  "sweep: aarmvs_sweep_options.size " + std::to_string(options->size) + " outside [" +
+                      std::to_string(AARMVS_SWEEP_OPTIONS_SIZE_V1) + ", " + std::to_string(sizeof(o)) +
+                      "] (set it to sizeof(aarmvs_sweep_options))");
+    std::memcpy(&o, options, options->size);
+  }
+  const int precision = o.precision;
+  const aarmvs_refine_args* refine = o.refine;
+  const aarmvs_posterior_args* posterior = o.posterior;
+  if (posterior && !posterior->state)
+    return fail(AARMVS_ERR_INVALID, "sweep: aarmvs_posterior_args without a state buffer "
+                                    "(aarmvs_posterior_state_bytes(B, H * W) bytes of device memory)");
+  if (posterior && a->record)
+    return fail(AARMVS_ERR_INVALID,
+                "sweep: the depth-posterior statistics are an inference output; a recorded (training) "
+                "sweep takes no aarmvs_posterior_args (aarmvs_posterior_from_cost works on its cost volume)");
   if (refine && !refine->state)
     return fail(AARMVS_ERR_INVALID, "sweep: aarmvs_refine_args without a state buffer "
                                     "(aarmvs_refine_state_bytes(B, H * W) bytes of device memory)");
@@ -855,6 +891,7 @@ int aarmvs_sweep_r(const aarmvs_sweep_args* a, int precision, const aarmvs_refin
   HipSweep run{a, T, g, ws, ca, evs.ev, {}};
   run.precision = precision;
   run.refine_state = refine ? refine->state : nullptr;
+  run.posterior_state = posterior ? posterior->state : nullptr;
   for (int i = 0; i < kSweepSlots; ++i) {
     const SweepStream id = plan.slot[i];
     if (id == kCaller) run.st[i] = stream;
@@ -912,6 +949,14 @@ int aarmvs_sweep_r(const aarmvs_sweep_args* a, int precision, const aarmvs_refin
                                     a->B, a->D, a->d_end, a->H * a->W, refine->depth_refined_out,
                                     refine->conf_window_out, refine->index_out, stream)) != hipSuccess)
       return hip_fail(e, "sweep: refine finalize");
+  }
+  // likewise the posterior statistics of the planes [0, d_end)
+  if (posterior && (posterior->mean_out || posterior->std_out || posterior->entropy_out ||
+                    posterior->runner_up_out)) {
+    if ((e = launch_posterior_finalize(ws.exp_sum, posterior->state, a->B, a->H * a->W, posterior->mean_out,
+                                       posterior->std_out, posterior->entropy_out,
+                                       posterior->runner_up_out, stream)) != hipSuccess)
+      return hip_fail(e, "sweep: posterior finalize");
   }
   return AARMVS_OK;
 }
@@ -1071,6 +1116,34 @@ int aarmvs_refine_from_cost(const float* cost, const float* depth_values, int B,
     return fail(AARMVS_ERR_INVALID, "refine_from_cost: need B, D, HW >= 1");
   hipError_t e = launch_refine_from_cost(cost, depth_values, B, D, HW, depth_refined, conf_window, index, stream);
   return e == hipSuccess ? AARMVS_OK : hip_fail(e, "refine_from_cost");
+}
+
+int aarmvs_wta_posterior_update(const float* cost, int d, float* max_prob, float* depth_map,
+                                float* exp_sum, void* state, const float* depth_d, int B, int HW,
+                                hipStream_t stream) {
+  if (!cost || !depth_d || !max_prob || !depth_map || !exp_sum || !state || B < 1 || HW < 1 || d < 0)
+    return fail(AARMVS_ERR_INVALID, "wta_posterior_update: bad arguments");
+  hipError_t e = launch_wta_posterior_update(cost, depth_d, d, max_prob, depth_map, exp_sum, state, B, HW, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "wta_posterior_update");
+}
+
+int aarmvs_wta_posterior_finalize(const float* exp_sum, const void* state, int B, int HW, float* mean,
+                                  float* std_out, float* entropy, float* runner_up, hipStream_t stream) {
+  if (!exp_sum || !state) return fail(AARMVS_ERR_INVALID, "wta_posterior_finalize: null pointer argument");
+  if (B < 1 || HW < 1) return fail(AARMVS_ERR_INVALID, "wta_posterior_finalize: need B, HW >= 1");
+  hipError_t e = launch_posterior_finalize(exp_sum, state, B, HW, mean, std_out, entropy, runner_up, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "wta_posterior_finalize");
+}
+
+int aarmvs_posterior_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
+                               float* mean, float* std_out, float* entropy, float* runner_up,
+                               hipStream_t stream) {
+  if (!cost || !depth_values)
+    return fail(AARMVS_ERR_INVALID, "posterior_from_cost: null pointer argument");
+  if (B < 1 || D < 1 || HW < 1)
+    return fail(AARMVS_ERR_INVALID, "posterior_from_cost: need B, D, HW >= 1");
+  hipError_t e = launch_posterior_from_cost(cost, depth_values, B, D, HW, mean, std_out, entropy, runner_up, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "posterior_from_cost");
 }
 
 int aarmvs_unet_step(const float* x, int B, int H, int W, int nsrc, int step,

@@ -1372,6 +1372,65 @@ __device__ __forceinline__ void refine_finish(const RefineState& r, float max_pr
   }
 }
 
+// ---------------------------------------------------------------------------
+// Depth-posterior statistics of the sweep (opt-in, beyond the reference): the
+// softmax-weighted mean and variance of depth, the weighted mean cost (for the entropy) and the
+// runner-up probability, kept online beside the WTA images (16 B per pixel in a caller-owned
+// buffer).  The head kernel, the standalone per-plane pair and the from-the-volume kernel all go
+// through posterior_step / posterior_finish, so they agree bit for bit on the same cost values.
+// ---------------------------------------------------------------------------
+struct PosteriorState {
+  float mu, var, ecost, p2;   // weighted mean depth, weighted variance, weighted mean cost, runner-up p
+};
+static_assert(sizeof(PosteriorState) == 16, "aarmvs_posterior_state_bytes is 16 B per pixel");
+
+__device__ __forceinline__ PosteriorState posterior_load(const void* state, size_t q) {
+  const float4 v = reinterpret_cast<const float4*>(state)[q];
+  return {v.x, v.y, v.z, v.w};
+}
+__device__ __forceinline__ void posterior_store(void* state, size_t q, const PosteriorState& r) {
+  reinterpret_cast<float4*>(state)[q] = make_float4(r.mu, r.var, r.ecost, r.p2);
+}
+
+// plane d's update from the plane's cost, its depth value, and max_prob / exp_sum BEFORE
+// wta_select: p and S1 are the values wta_select forms.  The variance is rescaled by S0 / S1, not
+// by 1 - k: with a dominant plane k rounds to within an ulp of 1 and 1 - k has no correct digit.
+// Plain operators under contract(off), not __fmul_rn / __fadd_rn: this toolchain's headers define
+// those as x * y and x + y in a scope the pragma does not reach, so a product and a sum written
+// with them may still fuse, differently from one kernel to the next.
+__device__ __forceinline__ void posterior_step(float cost, float x, float max_prob_before,
+                                               float exp_sum_before, PosteriorState& r) {
+#pragma clang fp contract(off)
+  const float p = expf(cost);
+  if (max_prob_before < p) r.p2 = max_prob_before;
+  else if (r.p2 < p) r.p2 = p;
+  if (p > 0.0f) {
+    const float s1 = exp_sum_before + p;
+    const float k = p / s1, j = exp_sum_before / s1;
+    const float dl = x - r.mu;
+    const float dk = dl * k, d2 = dl * dl, ck = (cost - r.ecost) * k;
+    const float d2k = d2 * k;
+    r.mu = r.mu + dk;
+    r.var = j * (r.var + d2k);
+    r.ecost = r.ecost + ck;
+  }
+}
+
+// the four outputs of one pixel from the state and the WTA image's exp_sum
+__device__ __forceinline__ void posterior_finish(const PosteriorState& r, float exp_sum, float& mean,
+                                                 float& sd, float& entropy, float& runner_up) {
+#pragma clang fp contract(off)
+  if (!(exp_sum > 0.0f && isfinite(exp_sum))) {
+    mean = sd = entropy = runner_up = __int_as_float(0x7fc00000);
+    return;
+  }
+  mean = r.mu;
+  sd = sqrtf(r.var);
+  const float h = logf(exp_sum) - r.ecost;
+  entropy = h > 0.0f ? h : 0.0f;
+  runner_up = r.p2 / exp_sum;
+}
+
 // aarmvs_wta_update: the online WTA of one plane on a caller-given cost slice [B,HW]
 __global__ void __launch_bounds__(256) wta_update_kernel(const float* __restrict__ cost,
                                                          const float* __restrict__ depth_d,
@@ -1405,7 +1464,8 @@ hipError_t launch_wta_update(const float* cost, const float* depth_d, float* max
 // read by 72 scalar LDS loads; bit-identical).
 // REFINE: the sweep's refining variant also carries the sub-plane state (loaded with the WTA
 // state, stored with it); the default instantiation has no trace of it.
-template <bool REFINE>
+// POST: likewise the depth-posterior state (posterior_step), independent of REFINE.
+template <bool REFINE, bool POST>
 __global__ void __launch_bounds__(256) head_wta_kernel(const float* __restrict__ h4,
                                                         const float* __restrict__ w,
                                                         const float* __restrict__ bias, int H,
@@ -1415,7 +1475,8 @@ __global__ void __launch_bounds__(256) head_wta_kernel(const float* __restrict__
                                                         float* __restrict__ exp_sum,
                                                         float* __restrict__ depth,
                                                         double* __restrict__ zero_stats,
-                                                        int zero_n, void* __restrict__ refine) {
+                                                        int zero_n, void* __restrict__ refine,
+                                                        void* __restrict__ posterior) {
 #pragma clang fp contract(off)
   constexpr int TW2 = kHeadTW + 2, NPX = (kHeadTH + 2) * TW2;
   __shared__ float4 t[NPX][2];
@@ -1441,6 +1502,10 @@ __global__ void __launch_bounds__(256) head_wta_kernel(const float* __restrict__
   RefineState rs{-1, 0.f, 0.f, 0.f};   // plane 0 starts from the reset state
   if constexpr (REFINE) {
     if (wta && own && d > 0) rs = refine_load(refine, q);
+  }
+  PosteriorState ps{0.f, 0.f, 0.f, 0.f};   // plane 0 starts from all zeros
+  if constexpr (POST) {
+    if (wta && own && d > 0) ps = posterior_load(posterior, q);
   }
   for (int rem = threadIdx.x; rem < NPX; rem += 256) {
     const int yy = y0 - 1 + rem / TW2, xx = x0 - 1 + rem % TW2;
@@ -1472,11 +1537,13 @@ __global__ void __launch_bounds__(256) head_wta_kernel(const float* __restrict__
   if (cost_out) cost_out[((size_t)b * D + d) * HW + p] = cost;
   if (wta) {
     if constexpr (REFINE) refine_step(cost, d, mp, rs);
+    if constexpr (POST) posterior_step(cost, dvals[b * D + d], mp, es, ps);
     wta_select(cost, dvals[b * D + d], mp, dp, es);
     max_prob[q] = mp;
     depth[q] = dp;
     exp_sum[q] = es;
     if constexpr (REFINE) refine_store(refine, q, rs);
+    if constexpr (POST) posterior_store(posterior, q, ps);
   }
 }
 
@@ -1553,6 +1620,73 @@ __global__ void __launch_bounds__(256) refine_from_cost_kernel(
     if (depth_refined) depth_refined[q] = dr;
     if (conf_window) conf_window[q] = cw;
     if (index) index[q] = rs.idx;
+  }
+}
+
+// the posterior finalize: mean / std / entropy / runner_up of B*HW pixels from the state and exp_sum
+__global__ void __launch_bounds__(256) posterior_finalize_kernel(
+    const float* __restrict__ exp_sum, const void* __restrict__ state, int HW,
+    float* __restrict__ mean, float* __restrict__ sd, float* __restrict__ entropy,
+    float* __restrict__ runner_up) {
+  const int b = blockIdx.y;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const size_t q = (size_t)b * HW + p;
+    float m, s, h, r2;
+    posterior_finish(posterior_load(state, q), exp_sum[q], m, s, h, r2);
+    if (mean) mean[q] = m;
+    if (sd) sd[q] = s;
+    if (entropy) entropy[q] = h;
+    if (runner_up) runner_up[q] = r2;
+  }
+}
+
+// aarmvs_wta_posterior_update: aarmvs_wta_update of plane d plus the posterior state, on a
+// caller-given cost slice [B,HW]; d == 0 starts from the all-zero state
+__global__ void __launch_bounds__(256) wta_posterior_update_kernel(
+    const float* __restrict__ cost, const float* __restrict__ depth_d, int d,
+    float* __restrict__ max_prob, float* __restrict__ depth, float* __restrict__ exp_sum,
+    void* __restrict__ state, int HW) {
+  const int b = blockIdx.y;
+  const float dv = depth_d[b];
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const size_t q = (size_t)b * HW + p;
+    float mp = max_prob[q], dp = depth[q], es = exp_sum[q];
+    PosteriorState ps{0.f, 0.f, 0.f, 0.f};
+    if (d != 0) ps = posterior_load(state, q);
+    const float c = cost[q];
+    posterior_step(c, dv, mp, es, ps);
+    wta_select(c, dv, mp, dp, es);
+    max_prob[q] = mp;
+    depth[q] = dp;
+    exp_sum[q] = es;
+    posterior_store(state, q, ps);
+  }
+}
+
+// aarmvs_posterior_from_cost: the same over a whole cost volume [B,D,HW], one thread per
+// (b, pixel), coalesced over pixels; the WTA images and the state stay in registers
+__global__ void __launch_bounds__(256) posterior_from_cost_kernel(
+    const float* __restrict__ cost, const float* __restrict__ dvals, int D, int HW,
+    float* __restrict__ mean, float* __restrict__ sd, float* __restrict__ entropy,
+    float* __restrict__ runner_up) {
+  const int b = blockIdx.y;
+  const float* dv = dvals + (size_t)b * D;
+  for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
+    const float* c = cost + (size_t)b * D * HW + p;
+    float mp = 0.f, dp = 0.f, es = 0.f;
+    PosteriorState ps{0.f, 0.f, 0.f, 0.f};
+    for (int d = 0; d < D; ++d) {
+      const float v = c[(size_t)d * HW];
+      posterior_step(v, dv[d], mp, es, ps);
+      wta_select(v, dv[d], mp, dp, es);
+    }
+    const size_t q = (size_t)b * HW + p;
+    float m, s, h, r2;
+    posterior_finish(ps, es, m, s, h, r2);
+    if (mean) mean[q] = m;
+    if (sd) sd[q] = s;
+    if (entropy) entropy[q] = h;
+    if (runner_up) runner_up[q] = r2;
   }
 }
 
@@ -1849,16 +1983,18 @@ hipError_t launch_unet_step(const float* x, const float* params, const SweepGeom
 
 hipError_t launch_head_wta(const float* params, const SweepGeom& g, const UnetIO& io,
                            const Workspace& ws, const float* depth_values, int d,
-                           float* cost_out, bool wta, hipStream_t s, void* refine_state) {
+                           float* cost_out, bool wta, hipStream_t s, void* refine_state,
+                           void* posterior_state) {
   const ParamLayout& L = param_layout();
   const int blocks = ((g.W + kHeadTW - 1) / kHeadTW) * ((g.H + kHeadTH - 1) / kHeadTH);
   ProfScope ps(s, K_HEAD_WTA);
-  auto kernel = refine_state ? head_wta_kernel<true> : head_wta_kernel<false>;
+  auto kernel = refine_state ? (posterior_state ? head_wta_kernel<true, true> : head_wta_kernel<true, false>)
+                             : (posterior_state ? head_wta_kernel<false, true> : head_wta_kernel<false, false>);
   hipLaunchKernelGGL(kernel, dim3(blocks, g.B), dim3(256), 0, s, io.h_new[4],
                      params + L.pk_off[P_HW], params + L.pk_off[P_HB], g.H, g.W, depth_values, d,
                      g.D, cost_out, wta ? 1 : 0, ws.max_prob, ws.exp_sum, ws.depth,
                      io.clear_stats ? io.reg_stats : nullptr,
-                     (int)(ws.reg_stats_bytes / sizeof(double)), refine_state);
+                     (int)(ws.reg_stats_bytes / sizeof(double)), refine_state, posterior_state);
   return hipGetLastError();
 }
 
@@ -1900,6 +2036,36 @@ hipError_t launch_refine_from_cost(const float* cost, const float* depth_values,
   ProfScope ps(s, K_REFINE);
   hipLaunchKernelGGL(refine_from_cost_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_values,
                      D, HW, depth_refined, conf_window, index);
+  return hipGetLastError();
+}
+
+hipError_t launch_posterior_finalize(const float* exp_sum, const void* state, int B, int HW,
+                                     float* mean, float* sd, float* entropy, float* runner_up,
+                                     hipStream_t s) {
+  const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
+  ProfScope ps(s, K_REFINE);
+  hipLaunchKernelGGL(posterior_finalize_kernel, dim3(blocks, B), dim3(256), 0, s, exp_sum, state, HW,
+                     mean, sd, entropy, runner_up);
+  return hipGetLastError();
+}
+
+hipError_t launch_wta_posterior_update(const float* cost, const float* depth_d, int d, float* max_prob,
+                                       float* depth, float* exp_sum, void* state, int B, int HW,
+                                       hipStream_t s) {
+  const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
+  ProfScope ps(s, K_HEAD_WTA);
+  hipLaunchKernelGGL(wta_posterior_update_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_d, d,
+                     max_prob, depth, exp_sum, state, HW);
+  return hipGetLastError();
+}
+
+hipError_t launch_posterior_from_cost(const float* cost, const float* depth_values, int B, int D,
+                                      int HW, float* mean, float* sd, float* entropy,
+                                      float* runner_up, hipStream_t s) {
+  const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
+  ProfScope ps(s, K_REFINE);
+  hipLaunchKernelGGL(posterior_from_cost_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_values,
+                     D, HW, mean, sd, entropy, runner_up);
   return hipGetLastError();
 }
 

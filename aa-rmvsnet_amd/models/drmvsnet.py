@@ -7,7 +7,8 @@ keys load unchanged) as the reference:
 
 * ``EMVSNet(disparity_level, image_scale=0.25, max_h=960, max_w=480, return_depth=False)``
   (drmvsnet.py:234-253; ``refine_depth=True`` with ``return_depth=True`` adds the sub-plane
-  ``depth_refined`` and ``photometric_confidence_window`` to the result, off by default) and ``forward(imgs, proj_matrices, depth_values)``
+  ``depth_refined`` and ``photometric_confidence_window`` to the result, ``posterior_stats=True`` likewise
+  ``depth_mean``, ``depth_std``, ``entropy`` and ``runner_up``; both off by default) and ``forward(imgs, proj_matrices, depth_values)``
   (drmvsnet.py:255-345);
 * ``mvsnet_cls_loss`` (drmvsnet.py:347-381);
 * ``FeatNet``, ``IntraViewAAModule``, ``InterViewAAModule``, ``UNetConvLSTM`` and the
@@ -349,8 +350,15 @@ class EMVSNet(nn.Module):
 
     def __init__(self, disparity_level, image_scale=0.25, max_h=960, max_w=480, return_depth=False,
                  evidential=True, return_cost=False, checkpoint_planes=0, sweep_precision="split",
-                 refine_depth=False):
+                 refine_depth=False, posterior_stats=False):
         super().__init__()
+        # the depth posterior's mean, standard deviation, entropy and runner-up probability on the
+        # return_depth=True path (opt-in, beyond the reference; include/aarmvs.h,
+        # aarmvs_posterior_args): four more keys in the result dict
+        if posterior_stats and not return_depth:
+            raise ValueError("EMVSNet: posterior_stats needs return_depth=True (the statistics come from "
+                             "the inference sweep; aarmvs.ops.posterior_from_cost works on a cost volume)")
+        self.posterior_stats = bool(posterior_stats)
         # sub-plane refinement of the WTA depth on the return_depth=True path (opt-in, beyond the
         # reference; include/aarmvs.h, aarmvs_sweep_r): two more keys in the result dict
         if refine_depth and not return_depth:
@@ -452,7 +460,7 @@ class EMVSNet(nn.Module):
             return prob, evidential, prob_combine
 
         out = sweep(ref, srcs, ref_proj, src_projs, dv, want_depth=True, want_cost=evidential_on,
-                    want_refined=self.refine_depth)
+                    want_refined=self.refine_depth, want_posterior=self.posterior_stats)
         evidential = None
         if evidential_on:
             evidential, _ = self.evidential(_ops.softmax_depth(out["cost"]), depth_values)
@@ -461,6 +469,9 @@ class EMVSNet(nn.Module):
         if self.refine_depth:
             res["depth_refined"] = out["depth_refined"]
             res["photometric_confidence_window"] = out["conf_window"]
+        if self.posterior_stats:
+            for k in _ops.POSTERIOR_KEYS:
+                res[k] = out[k]
         return res
 
 

@@ -260,6 +260,62 @@ typedef struct aarmvs_refine_args {
 size_t aarmvs_refine_state_bytes(int B, int HW);   /* 16 * B * HW; 0 for B, HW < 1 */
 int aarmvs_sweep_r(const aarmvs_sweep_args* args, int precision, const aarmvs_refine_args* refine,
                    hipStream_t stream);
+
+/* Depth-posterior statistics of the sweep (opt-in, inference only, beyond the reference): the
+ * moments of the distribution q[d] = p[d] / sum p over the planes, p[d] = exp(cost[d]) -- the
+ * softmax the WTA confidence already normalises by -- accumulated online in the head kernel, with
+ * no cost volume.  Everything is fp32 and every operation is rounded on its own.  Per pixel the
+ * state is (mu, V, E, p2), all zero before plane 0 (never loaded for it).  For plane d, in order,
+ * with c the plane's cost, p = expf(c) (the value the WTA forms), x = depth_values[b*D + d],
+ * S0 = exp_sum before the plane, S1 = S0 + p (the value the WTA stores), m = max_prob before the
+ * plane's select:
+ *   runner-up:  if (m < p) p2 = m;  else if (p2 < p) p2 = p;
+ *               (a p equal to the maximum is a runner-up: the first maximum wins)
+ *   moments, only if (p > 0):
+ *     k = p / S1        j = S0 / S1        delta = x - mu
+ *     mu <- mu + delta * k
+ *     V  <- j * (V + (delta * delta) * k)
+ *     E  <- E + (c - E) * k
+ * V is rescaled by S0 / S1 and NOT by 1 - k: when a late plane dominates, k rounds to within
+ * 2^-24 of 1 and 1 - k keeps no correct digit, which loses the standard deviation completely
+ * (DESIGN.md section 9).  After n planes, with S = exp_sum:
+ *   if !(S > 0 && isfinite(S)) all four outputs are NaN: every pixel whose WTA confidence is NaN
+ *   (0/0, inf/inf, a NaN cost), and a finite max_prob over an overflowed sum;
+ *   otherwise depth_mean = mu, depth_std = sqrtf(V), entropy = max(logf(S) - E, 0) in nats,
+ *   runner_up = p2 / S.  V >= 0 by construction; it is not clamped.
+ * state: aarmvs_posterior_state_bytes(B, H*W) = 16 B per pixel of caller-owned device memory,
+ * 16-byte aligned.  Like the WTA images it is complete only after contiguous calls from plane 0
+ * through one workspace and one state buffer: a sweep split into d_range calls equals the whole
+ * sweep bit for bit.  The outputs ([B,H,W] each, any may be NULL) are written at the end of EVERY
+ * call and describe the planes [0, d_end).  The sweep workspace and its layout are unchanged,
+ * depth_out / conf_out / cost_out are bit-identical with and without the statistics, and the head
+ * kernel reads and writes 16 B per pixel and plane more (measured cost: DESIGN.md section 9).
+ * Both precisions; a NULL state or a training record with posterior != NULL:
+ * AARMVS_ERR_INVALID (aarmvs_posterior_from_cost serves a cost volume). */
+typedef struct aarmvs_posterior_args {
+  void* state;           /* aarmvs_posterior_state_bytes(B, H*W) bytes, required */
+  float* mean_out;       /* [B,H,W] or NULL: softmax-weighted mean depth (soft argmax) */
+  float* std_out;        /* [B,H,W] or NULL: standard deviation of depth under q */
+  float* entropy_out;    /* [B,H,W] or NULL: entropy of q in nats */
+  float* runner_up_out;  /* [B,H,W] or NULL: the second largest q */
+} aarmvs_posterior_args;
+size_t aarmvs_posterior_state_bytes(int B, int HW);   /* 16 * B * HW; 0 for B, HW < 1 */
+
+/* The sweep's extensible entry point: the options of a sweep beyond aarmvs_sweep_args.  `size`
+ * is the caller's sizeof(aarmvs_sweep_options); any size from the first version's
+ * (AARMVS_SWEEP_OPTIONS_SIZE_V1) up to the library's own is accepted and fields beyond it read
+ * as zero, so a caller built against an older header keeps working; any other size is
+ * AARMVS_ERR_INVALID.  options == NULL is all defaults.  aarmvs_sweep(a, s), aarmvs_sweep_p(a, p,
+ * s) and aarmvs_sweep_r(a, p, r, s) are this call with {precision = p, refine = r}. */
+typedef struct aarmvs_sweep_options {
+  size_t size;                             /* sizeof(aarmvs_sweep_options) of the caller */
+  int precision;                           /* aarmvs_precision; 0 = AARMVS_PREC_SPLIT */
+  const aarmvs_refine_args* refine;        /* NULL: no sub-plane refinement */
+  const aarmvs_posterior_args* posterior;  /* NULL: no posterior statistics */
+} aarmvs_sweep_options;
+#define AARMVS_SWEEP_OPTIONS_SIZE_V1 (sizeof(size_t) + 2 * sizeof(int) + 2 * sizeof(void*))
+int aarmvs_sweep_ex(const aarmvs_sweep_args* args, const aarmvs_sweep_options* options,
+                    hipStream_t stream);
 /* A stream for aux_stream owned by the library (one per device, created on first use, never
  * destroyed): a process gets four hardware queues and streams beyond four share them, so a
  * caller without streams of its own passes this one rather than creating a fifth (the library's
@@ -385,6 +441,24 @@ int aarmvs_wta_refine_finalize(const float* max_prob, const float* depth_map, co
                                hipStream_t stream);
 int aarmvs_refine_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
                             float* depth_refined, float* conf_window, int* index, hipStream_t stream);
+
+/* The posterior statistics for cost planes that do not come from a sweep (see
+ * aarmvs_posterior_args for the definition): aarmvs_wta_posterior_update is aarmvs_wta_update of
+ * plane d (the planes must come in order, d = 0, 1, ...) that also maintains `state`
+ * (aarmvs_posterior_state_bytes(B, HW) bytes; d == 0 resets it -- the WTA images are the caller's
+ * to zero); aarmvs_wta_posterior_finalize writes mean / std / entropy / runner_up [B,HW] (each
+ * may be NULL) of the planes given so far from exp_sum and the state.
+ * aarmvs_posterior_from_cost gives the same four outputs from a whole cost volume [B,D,HW] and
+ * depth_values [B,D], e.g. a training sweep's: the same expressions in the same order, so it
+ * equals the online result bit for bit on the same cost values. */
+int aarmvs_wta_posterior_update(const float* cost, int d, float* max_prob, float* depth_map,
+                                float* exp_sum, void* state, const float* depth_d, int B, int HW,
+                                hipStream_t stream);
+int aarmvs_wta_posterior_finalize(const float* exp_sum, const void* state, int B, int HW, float* mean,
+                                  float* std_out, float* entropy, float* runner_up, hipStream_t stream);
+int aarmvs_posterior_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
+                               float* mean, float* std_out, float* entropy, float* runner_up,
+                               hipStream_t stream);
 
 /* softmax over the depth axis of cost [B,D,H,W] (drmvsnet.py:291/:342). */
 int aarmvs_softmax_depth(const float* cost, float* prob, int B, int D, int HW,

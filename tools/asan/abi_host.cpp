@@ -155,6 +155,33 @@ int main() {
                                    nullptr) == AARMVS_ERR_INVALID);
   CHECK(aarmvs_refine_from_cost(dummy, nullptr, 1, 4, 64, dummy, dummy, nullptr, nullptr) == AARMVS_ERR_INVALID);
   CHECK(aarmvs_refine_from_cost(dummy, dummy, 1, 0, 64, dummy, dummy, nullptr, nullptr) == AARMVS_ERR_INVALID);
+  // the depth-posterior statistics' entries and aarmvs_sweep_ex's size rule
+  CHECK(aarmvs_posterior_state_bytes(2, 720) == 23040);
+  CHECK(aarmvs_posterior_state_bytes(0, 720) == 0 && aarmvs_posterior_state_bytes(2, 0) == 0);
+  aarmvs_posterior_args po;
+  std::memset(&po, 0, sizeof(po));
+  aarmvs_sweep_options so;
+  std::memset(&so, 0, sizeof(so));
+  so.size = sizeof(so);
+  so.posterior = &po;
+  CHECK(aarmvs_sweep_ex(&a, &so, nullptr) == AARMVS_ERR_INVALID);   // state null
+  CHECK(aarmvs_sweep_ex(nullptr, &so, nullptr) == AARMVS_ERR_INVALID);
+  so.size = AARMVS_SWEEP_OPTIONS_SIZE_V1 - 1;
+  CHECK(aarmvs_sweep_ex(&a, &so, nullptr) == AARMVS_ERR_INVALID);
+  so.size = sizeof(so) + 1;   // a larger size is refused before anything beyond the struct is read
+  CHECK(aarmvs_sweep_ex(&a, &so, nullptr) == AARMVS_ERR_INVALID);
+  CHECK(aarmvs_wta_posterior_update(dummy, 0, dummy, dummy, dummy, nullptr, dummy, 1, 64, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_wta_posterior_update(dummy, -1, dummy, dummy, dummy, dummy, dummy, 1, 64, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_wta_posterior_finalize(dummy, nullptr, 1, 64, dummy, dummy, dummy, dummy, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_wta_posterior_finalize(dummy, dummy, 1, 0, dummy, dummy, dummy, dummy, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_posterior_from_cost(dummy, nullptr, 1, 4, 64, dummy, dummy, dummy, dummy, nullptr) ==
+        AARMVS_ERR_INVALID);
+  CHECK(aarmvs_posterior_from_cost(dummy, dummy, 1, 0, 64, dummy, dummy, dummy, dummy, nullptr) ==
+        AARMVS_ERR_INVALID);
   CHECK(aarmvs_unet_step(dummy, 1, 8, 8, 1, -1, dummy, dummy, dummy, nullptr) == AARMVS_ERR_INVALID);
   CHECK(aarmvs_unet_step(dummy, 1, 8, 9, 1, 0, dummy, dummy, dummy, nullptr) == AARMVS_ERR_INVALID);
   CHECK(aarmvs_softmax_depth(dummy, dummy, 1, 0, 64, nullptr) == AARMVS_ERR_INVALID);
