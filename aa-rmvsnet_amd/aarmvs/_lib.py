@@ -108,6 +108,15 @@ class FusionArgs(ctypes.Structure):
     ]
 
 
+class FusionDedupArgs(ctypes.Structure):
+    """Mirror of ``aarmvs_fusion_dedup_args``."""
+    _fields_ = [
+        ("used_ref", c_void_p),
+        ("used_src", c_void_p * MAX_FUSION_SRC),
+        ("emit_mask", c_void_p),
+    ]
+
+
 class FusionPointsArgs(ctypes.Structure):
     """Mirror of ``aarmvs_fusion_points_args``."""
     _fields_ = [
@@ -176,6 +185,8 @@ SIGNATURES = {
     "aarmvs_wta_posterior_finalize": (c_int, [c_void_p, c_void_p, c_int, c_int] + [c_void_p] * 5),
     "aarmvs_posterior_from_cost": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int] + [c_void_p] * 5),
     "aarmvs_fusion_filter": (c_int, [ctypes.POINTER(FusionArgs), c_void_p]),
+    "aarmvs_fusion_filter_dedup": (c_int, [ctypes.POINTER(FusionArgs), ctypes.POINTER(FusionDedupArgs),
+                                           c_void_p]),
     "aarmvs_pyr_down": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "aarmvs_fusion_points_workspace_bytes": (c_size_t, [c_int, c_int]),
     "aarmvs_fusion_points": (c_int, [ctypes.POINTER(FusionPointsArgs), c_void_p]),

@@ -18,6 +18,14 @@ is that per-scan driver (halved intrinsics, rows [2:-2] of the maps, ``pyr_down`
 (``aarmvs_pyr_down``), the same filter core, and ``fuse_points_gpu`` (``aarmvs_fusion_points``)
 for the kept pixels' points).  ``python -m aarmvs.fusion --test_dataset {dtu,tnt} ...`` runs
 either driver over a scan list.
+
+Opt-in, beyond the reference: the visibility de-duplication (``--dedup``, ``dedup=True`` on both
+drivers and on ``fuse_views``, which fuses a scan held in memory; ``filter_depth_dedup`` per
+reference view, ``aarmvs_fusion_filter_dedup``).  A scan keeps one used map per view; a final pixel
+marks the pixel it projects to in every source view it is consistent with, and a later view emits
+only its final pixels that are not marked, so a surface patch seen from k views is emitted about
+once instead of k times.  Off (the default) nothing changes.  Its effect on DTU and Tanks and
+Temples scores is not measured.
 """
 from __future__ import annotations
 
@@ -57,6 +65,36 @@ def pack_cameras(ref_cam, src_cams) -> np.ndarray:
 def filter_depth_core(ref_depth: torch.Tensor, confidence: torch.Tensor, ref_cam, src_depths,
                       src_cams, photo_threshold: float):
     """(photo_mask, geo_mask, final_mask [H,W] bool, depth_est_averaged [H,W] float64)."""
+    return _filter_launch(ref_depth, confidence, ref_cam, src_depths, src_cams, photo_threshold, None)
+
+
+def _used_map(t, ref_depth, what):
+    if not (isinstance(t, torch.Tensor) and t.device == ref_depth.device and t.dtype == torch.uint8
+            and t.shape == ref_depth.shape and t.is_contiguous()):
+        raise AarmvsError(f"aarmvs: fusion {what} must be a contiguous CUDA uint8 [H,W] tensor of the depth "
+                          "map's size, on its device")
+    return t
+
+
+def filter_depth_dedup(ref_depth: torch.Tensor, confidence: torch.Tensor, ref_cam, src_depths, src_cams,
+                       photo_threshold: float, used_ref, used_srcs, emit_out=None):
+    """``filter_depth_core`` with the visibility de-duplication (``aarmvs_fusion_filter_dedup``,
+    include/aarmvs.h): (photo_mask, geo_mask, final_mask, emit_mask [H,W] bool,
+    depth_est_averaged [H,W] float64).  ``used_ref``: the reference view's used map, a CUDA uint8
+    [H,W] tensor, or None (nothing used yet: emit = final).  ``used_srcs``: one used map per source
+    view, marked IN PLACE; an entry may be None (that view is not marked).  emit = final and not
+    used_ref; every final pixel marks the nearest pixel of each source view it is consistent with.
+    The other four outputs are ``filter_depth_core``'s, bit for bit.  The calls of one scan must be
+    ordered on one stream.  ``emit_out``: a CUDA uint8 [H,W] tensor to write the emit mask into."""
+    if len(used_srcs) != len(src_depths):
+        raise AarmvsError(f"aarmvs: fusion got {len(src_depths)} source views but {len(used_srcs)} used maps")
+    return _filter_launch(ref_depth, confidence, ref_cam, src_depths, src_cams, photo_threshold,
+                          (used_ref, list(used_srcs), emit_out))
+
+
+def _filter_launch(ref_depth, confidence, ref_cam, src_depths, src_cams, photo_threshold, dedup):
+    """The filter launch behind ``filter_depth_core`` (dedup None) and ``filter_depth_dedup``
+    (dedup = (used_ref, used_srcs, emit_out))."""
     nsrc = len(src_depths)
     if not 1 <= nsrc <= _lib.MAX_FUSION_SRC:
         raise AarmvsError(f"aarmvs: fusion needs 1..{_lib.MAX_FUSION_SRC} source views, got {nsrc}")
@@ -84,9 +122,23 @@ def filter_depth_core(ref_depth: torch.Tensor, confidence: torch.Tensor, ref_cam
     a.photo_threshold = float(np.float32(photo_threshold))
     a.photo_mask, a.geo_mask, a.final_mask = photo.data_ptr(), geo.data_ptr(), final.data_ptr()
     a.depth_avg = avg.data_ptr()
-    check(lib().aarmvs_fusion_filter(ctypes.byref(a), torch.cuda.current_stream().cuda_stream),
-          "fusion_filter")
-    return photo.bool(), geo.bool(), final.bool(), avg
+    if dedup is None:
+        check(lib().aarmvs_fusion_filter(ctypes.byref(a), torch.cuda.current_stream().cuda_stream),
+              "fusion_filter")
+        return photo.bool(), geo.bool(), final.bool(), avg
+    used_ref, used_srcs, emit = dedup
+    d = _lib.FusionDedupArgs()
+    if used_ref is not None:
+        d.used_ref = _used_map(used_ref, ref_depth, "used_ref").data_ptr()
+    for i, t in enumerate(used_srcs):
+        if t is not None:
+            d.used_src[i] = _used_map(t, ref_depth, "used_srcs").data_ptr()
+    emit = torch.empty_like(photo) if emit is None else _used_map(emit, ref_depth, "emit_out")
+    d.emit_mask = emit.data_ptr()
+    with torch.cuda.device(dev):
+        check(lib().aarmvs_fusion_filter_dedup(ctypes.byref(a), ctypes.byref(d),
+                                               torch.cuda.current_stream().cuda_stream), "fusion_filter_dedup")
+    return photo.bool(), geo.bool(), final.bool(), emit.bool(), avg
 
 
 def fuse_points(depth_est_averaged, final_mask, ref_cam, ref_img=None):
@@ -161,7 +213,7 @@ def resize_linear(img, width, height):
 
 
 def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="cuda",
-                 depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR):
+                 depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR, dedup=False):
     """fusion.py:135-273 for one scan: for every (ref_view, src_views) of pair.txt with an
     estimated depth map, the geometric / photometric filtering on the GPU
     (``filter_depth_core``), the three mask PNGs under out_folder/mask, and the kept pixels'
@@ -169,17 +221,27 @@ def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="
     plyfilename.  Returns the number of points written.  ``depth_dir`` / ``conf_dir``: the
     folders under out_folder the depth and confidence maps are read from (the reference's
     depth_est_0 / confidence_0; e.g. eval_sharded --refine_depth's depth_refined_0 /
-    confidence_window_0)."""
+    confidence_window_0).  ``dedup``: the opt-in visibility de-duplication
+    (``filter_depth_dedup``): every view's depth map (read once) and used map stay on the GPU for
+    the whole scan, the points are those of the emit mask, and mask/{view}_emit.png is written
+    beside the other three."""
     vertexs, vertex_colors = [], []
     dev = torch.device(device)
     depth_file = os.path.join(out_folder, depth_dir, "{:0>8}.pfm")
+    cache, used = {}, _UsedMaps()
+
+    def depth_of(view):   # dedup only: a PFM is read once per scan
+        if view not in cache:
+            cache[view] = torch.from_numpy(np.ascontiguousarray(read_pfm(depth_file.format(view))[0])).to(dev)
+        return cache[view]
+
     for ref_view, src_views in read_pair_file(os.path.join(scan_folder, "pair.txt")):
         dpath = depth_file.format(ref_view)
         if not os.path.exists(dpath):
             print("skip", ref_view)
             continue
         ref_img = read_img(os.path.join(scan_folder, "images/{:0>8}.jpg".format(ref_view)))
-        ref_depth_est = read_pfm(dpath)[0]
+        ref_depth_est = None if dedup else read_pfm(dpath)[0]
         confidence = read_pfm(os.path.join(out_folder, conf_dir, "{:0>8}.pfm".format(ref_view)))[0]
         scale, index, index_p, flag = crop_params(ref_img.shape[:2], confidence.shape[:2])
         ref_img = resize_linear(ref_img, int(ref_img.shape[1] * scale), int(ref_img.shape[0] * scale))
@@ -191,13 +253,21 @@ def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="
         ref_cam = read_camera_parameters(cam_file.format(ref_view), scale, index, flag)
         src_depths, src_cams = [], []
         for src_view in src_views:
-            src_depths.append(torch.from_numpy(np.ascontiguousarray(read_pfm(
+            src_depths.append(depth_of(src_view) if dedup else torch.from_numpy(np.ascontiguousarray(read_pfm(
                 depth_file.format(src_view))[0])).to(dev))
             src_cams.append(read_camera_parameters(cam_file.format(src_view), scale, index, flag))
-        photo, geo, final, avg = filter_depth_core(
-            torch.from_numpy(np.ascontiguousarray(ref_depth_est)).to(dev),
-            torch.from_numpy(np.ascontiguousarray(confidence)).to(dev), ref_cam, src_depths, src_cams,
-            photo_threshold)
+        if dedup:
+            ref_depth = depth_of(ref_view)
+            photo, geo, final, emit, avg = filter_depth_dedup(
+                ref_depth, torch.from_numpy(np.ascontiguousarray(confidence)).to(dev), ref_cam, src_depths,
+                src_cams, photo_threshold, used.of(ref_view, ref_depth),
+                [used.of(v, d) for v, d in zip(src_views, src_depths)])
+            emit = emit.cpu().numpy()
+        else:
+            photo, geo, final, avg = filter_depth_core(
+                torch.from_numpy(np.ascontiguousarray(ref_depth_est)).to(dev),
+                torch.from_numpy(np.ascontiguousarray(confidence)).to(dev), ref_cam, src_depths, src_cams,
+                photo_threshold)
         photo, geo, final = (m.cpu().numpy() for m in (photo, geo, final))
         os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
         save_mask(os.path.join(out_folder, "mask/{:0>8}_photo.png".format(ref_view)), photo)
@@ -205,7 +275,10 @@ def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="
         save_mask(os.path.join(out_folder, "mask/{:0>8}_final.png".format(ref_view)), final)
         print("processing {}, ref-view{:0>2}, photo/geo/final-mask:{}/{}/{}".format(
             scan_folder, ref_view, photo.mean(), geo.mean(), final.mean()))
-        xyz, rgb = fuse_points(avg.cpu().numpy(), final, ref_cam, ref_img)
+        if dedup:
+            save_mask(os.path.join(out_folder, "mask/{:0>8}_emit.png".format(ref_view)), emit)
+            print("  emit-mask:{}".format(emit.mean()))
+        xyz, rgb = fuse_points(avg.cpu().numpy(), emit if dedup else final, ref_cam, ref_img)
         vertexs.append(xyz)
         vertex_colors.append(rgb)
     xyz = np.concatenate(vertexs, axis=0) if vertexs else np.zeros((0, 3), np.float32)
@@ -305,6 +378,66 @@ def fuse_points_gpu(depth_avg, final_mask, ref_cam, ref_img=None):
     return xyz[:n], (None if rgb is None else rgb[:n])
 
 
+class _UsedMaps:
+    """A scan's used maps (the visibility de-duplication's state): one zeroed CUDA uint8 map per
+    view id, allocated when the view is first a reference or a source view."""
+
+    def __init__(self):
+        self.maps = {}
+
+    def of(self, view, depth):
+        if view not in self.maps:
+            self.maps[view] = torch.zeros(depth.shape, dtype=torch.uint8, device=depth.device)
+        return self.maps[view]
+
+
+def fuse_views(pairs, depths, confidences, cams, images=None, photo_threshold=0.35, dedup=False):
+    """Filter and fuse a scan held in memory.  ``pairs``: [(ref_view, [src_view, ...]), ...] in
+    pair-file order; ``depths`` / ``confidences``: {view: CUDA float32 [H,W]}; ``cams``: {view: (K,
+    E)}; ``images``: {view: CUDA float32 [H,W,3] in [0,1]} or None.  Reference views absent from
+    ``depths`` are skipped.  Per reference view ``filter_depth_core`` (``dedup=False``: the cloud is
+    the concatenation the file drivers write) or ``filter_depth_dedup`` on the scan's used maps
+    (``dedup=True``: a view emits only the final pixels that no earlier view's consistent match
+    marked), then ``fuse_points_gpu`` on the final / emit mask.  Returns a dict: ``xyz`` float32
+    [n,3] and ``rgb`` uint8 [n,3] (None without images) CUDA tensors, ``masks`` {view: {"photo",
+    "geo", "final"(, "emit"): bool [H,W]}}, ``avg`` {view: float64 [H,W]}, ``counts`` {view: points
+    emitted} and, with ``dedup``, ``used`` {view: uint8 [H,W]} after the scan."""
+    used = _UsedMaps()
+    masks, avgs, counts, verts, cols = {}, {}, {}, [], []
+    dev = None
+    for ref_view, src_views in pairs:
+        if ref_view not in depths:
+            continue
+        ref_depth = depths[ref_view]
+        dev = ref_depth.device
+        src_depths = [depths[v] for v in src_views]
+        src_cams = [cams[v] for v in src_views]
+        if dedup:
+            photo, geo, final, emit, avg = filter_depth_dedup(
+                ref_depth, confidences[ref_view], cams[ref_view], src_depths, src_cams, photo_threshold,
+                used.of(ref_view, ref_depth), [used.of(v, depths[v]) for v in src_views])
+            masks[ref_view] = dict(photo=photo, geo=geo, final=final, emit=emit)
+        else:
+            photo, geo, final, avg = filter_depth_core(ref_depth, confidences[ref_view], cams[ref_view],
+                                                       src_depths, src_cams, photo_threshold)
+            emit = final
+            masks[ref_view] = dict(photo=photo, geo=geo, final=final)
+        xyz, rgb = fuse_points_gpu(avg, emit, cams[ref_view], None if images is None else images[ref_view])
+        avgs[ref_view], counts[ref_view] = avg, int(xyz.shape[0])
+        verts.append(xyz)
+        cols.append(rgb)
+    if verts:
+        xyz = torch.cat(verts)
+        rgb = None if images is None else torch.cat(cols)
+    else:
+        xyz = torch.zeros(0, 3, dtype=torch.float32, device=dev)
+        rgb = None if images is None else torch.zeros(0, 3, dtype=torch.uint8, device=dev)
+    out = dict(xyz=xyz, rgb=rgb, masks=masks, avg=avgs, counts=counts)
+    if dedup:
+        out["used"] = used.maps
+    return out
+
+
 def read_camera_parameters_tnt(filename):
     """(intrinsics float32 3x3, extrinsics float32 4x4) of a cam.txt with intrinsics rows 0
     and 1 halved in float32 (fusion_padding.py:29-39: the maps are half the image's size)."""
@@ -314,7 +447,7 @@ def read_camera_parameters_tnt(filename):
 
 
 def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, device="cuda",
-                     depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR):
+                     depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR, dedup=False):
     """fusion_padding.py:137-266 for one scan.  Per reference view of pair.txt: the image goes
     to the GPU and through ``pyr_down``; rows [2:-2] are cropped from the reference and source
     depth maps and the confidence map (the padding loader's extra rows); ``filter_depth_core``
@@ -323,12 +456,13 @@ def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, 
     points.  Only the three masks (for the PNGs under out_folder/mask) and the kept points come
     back to the host.  Writes plyfilename and returns the number of points.  A reference view
     without a depth map is skipped (the reference stops with an error there).  ``depth_dir`` /
-    ``conf_dir``: as for ``filter_depth``."""
+    ``conf_dir``, ``dedup``: as for ``filter_depth`` (the cropped depth maps stay on the GPU for the
+    whole scan either way; with ``dedup`` the used maps do too)."""
     vertexs, vertex_colors = [], []
     dev = torch.device(device)
     cam_file = os.path.join(scan_folder, "cams/{:0>8}_cam.txt")
     depth_file = os.path.join(out_folder, depth_dir, "{:0>8}.pfm")
-    cache = {}
+    cache, used = {}, _UsedMaps()
 
     def cropped(path):
         return torch.from_numpy(np.ascontiguousarray(read_pfm(path)[0])).to(dev)[2:-2]
@@ -351,9 +485,16 @@ def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, 
             raise AarmvsError(f"aarmvs: view {ref_view}: the halved image is {tuple(ref_img.shape[:2])} "
                               f"but the cropped depth map is {tuple(ref_depth_est.shape)}")
         src_cams = [read_camera_parameters_tnt(cam_file.format(v)) for v in src_views]
-        photo, geo, final, avg = filter_depth_core(ref_depth_est, confidence, ref_cam,
-                                                   [depth_of(v) for v in src_views], src_cams, photo_threshold)
-        xyz, rgb = fuse_points_gpu(avg, final, ref_cam, ref_img)
+        if dedup:
+            photo, geo, final, emit, avg = filter_depth_dedup(
+                ref_depth_est, confidence, ref_cam, [depth_of(v) for v in src_views], src_cams, photo_threshold,
+                used.of(ref_view, ref_depth_est), [used.of(v, depth_of(v)) for v in src_views])
+            xyz, rgb = fuse_points_gpu(avg, emit, ref_cam, ref_img)
+            emit = emit.cpu().numpy()
+        else:
+            photo, geo, final, avg = filter_depth_core(ref_depth_est, confidence, ref_cam,
+                                                       [depth_of(v) for v in src_views], src_cams, photo_threshold)
+            xyz, rgb = fuse_points_gpu(avg, final, ref_cam, ref_img)
         photo, geo, final = (m.cpu().numpy() for m in (photo, geo, final))
         os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
         save_mask(os.path.join(out_folder, "mask/{:0>8}_photo.png".format(ref_view)), photo)
@@ -361,6 +502,9 @@ def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, 
         save_mask(os.path.join(out_folder, "mask/{:0>8}_final.png".format(ref_view)), final)
         print("processing {}, ref-view{:0>2}, photo/geo/final-mask:{}/{}/{}".format(
             scan_folder, ref_view, photo.mean(), geo.mean(), final.mean()))
+        if dedup:
+            save_mask(os.path.join(out_folder, "mask/{:0>8}_emit.png".format(ref_view)), emit)
+            print("  emit-mask:{}".format(emit.mean()))
         vertexs.append(xyz.cpu().numpy())
         vertex_colors.append(rgb.cpu().numpy())
     xyz = np.concatenate(vertexs, axis=0) if vertexs else np.zeros((0, 3), np.float32)
@@ -453,6 +597,9 @@ def build_parser():
                    help="per-scan folder of the depth maps (e.g. depth_refined_0 of eval_sharded --refine_depth)")
     p.add_argument("--conf_dir", default=DEFAULT_CONF_DIR,
                    help="per-scan folder of the confidence maps (e.g. confidence_window_0)")
+    p.add_argument("--dedup", action="store_true",
+                   help="visibility de-duplication: a view emits only the final pixels that no earlier view's "
+                        "consistent match marked (off: the reference's cloud; DESIGN.md §4b)")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -481,11 +628,13 @@ def main(argv=None):
         scan_folder = os.path.join(args.testpath, scan)
         out_folder = os.path.join(args.outdir, scan)
         ply = ply_path(args.outdir, scan, args.test_dataset)
-        # (the folders are passed on only when they are not the defaults: the default call is
-        # the five-argument one it has always been)
+        # (the folders and --dedup are passed on only when they are not the defaults: the default
+        # call is the five-argument one it has always been)
         dirs = {}
         if (args.depth_dir, args.conf_dir) != (DEFAULT_DEPTH_DIR, DEFAULT_CONF_DIR):
             dirs = dict(depth_dir=args.depth_dir, conf_dir=args.conf_dir)
+        if args.dedup:
+            dirs["dedup"] = True
         if args.test_dataset == "tnt":
             filter_depth_tnt(scan_folder, out_folder, ply, args.photo_threshold, args.device, **dirs)
         else:

@@ -154,6 +154,9 @@ struct CostArgs {
 // NCHW <-> NHWC copy of a [B][C][HW] / [B][HW][C] fp32 tensor (API edges only)
 // depth-map fusion core (fusion.hip)
 hipError_t launch_fusion_filter(const aarmvs_fusion_args* a, hipStream_t s);
+// the same with the visibility de-duplication (d is not NULL)
+hipError_t launch_fusion_filter_dedup(const aarmvs_fusion_args* a, const aarmvs_fusion_dedup_args* d,
+                                      hipStream_t s);
 // one cv2.pyrDown level of an interleaved float32 image, and the ordered world points of a
 // reference view's kept pixels (fusion.hip)
 hipError_t launch_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t s);

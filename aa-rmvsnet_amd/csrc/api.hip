@@ -1186,7 +1186,7 @@ int aarmvs_unet_step_p(const float* x, int B, int H, int W, int nsrc, int step,
   return AARMVS_OK;
 }
 
-int aarmvs_fusion_filter(const aarmvs_fusion_args* a, hipStream_t stream) {
+static int fusion_filter_check(const aarmvs_fusion_args* a) {
   if (!a) return fail(AARMVS_ERR_INVALID, "fusion_filter: null args");
   if (a->H < 1 || a->W < 1 || a->nsrc < 1 || a->nsrc > AARMVS_MAX_FUSION_SRC)
     return fail(AARMVS_ERR_INVALID, "fusion_filter: need H, W >= 1 and 1 <= nsrc <= 10");
@@ -1195,8 +1195,29 @@ int aarmvs_fusion_filter(const aarmvs_fusion_args* a, hipStream_t stream) {
     return fail(AARMVS_ERR_INVALID, "fusion_filter: null pointer argument");
   for (int v = 0; v < a->nsrc; ++v)
     if (!a->src_depth[v]) return fail(AARMVS_ERR_INVALID, "fusion_filter: null src_depth pointer");
+  return AARMVS_OK;
+}
+
+int aarmvs_fusion_filter(const aarmvs_fusion_args* a, hipStream_t stream) {
+  if (int rc = fusion_filter_check(a)) return rc;
   hipError_t e = launch_fusion_filter(a, stream);
   return e == hipSuccess ? AARMVS_OK : hip_fail(e, "fusion_filter");
+}
+
+int aarmvs_fusion_filter_dedup(const aarmvs_fusion_args* a, const aarmvs_fusion_dedup_args* d,
+                               hipStream_t stream) {
+  if (!d) return aarmvs_fusion_filter(a, stream);
+  if (int rc = fusion_filter_check(a)) return rc;
+  if (!d->emit_mask) return fail(AARMVS_ERR_INVALID, "fusion_filter_dedup: null emit_mask");
+  if (d->emit_mask == a->photo_mask || d->emit_mask == a->geo_mask || d->emit_mask == a->final_mask)
+    return fail(AARMVS_ERR_INVALID,
+                "fusion_filter_dedup: emit_mask must not be the photo, geo or final mask");
+  // a launch only reads used_ref and only writes the used_src maps: a view is not its own source
+  for (int v = 0; v < a->nsrc; ++v)
+    if (d->used_ref && d->used_src[v] == d->used_ref)
+      return fail(AARMVS_ERR_INVALID, "fusion_filter_dedup: used_ref must not be one of used_src");
+  hipError_t e = launch_fusion_filter_dedup(a, d, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "fusion_filter_dedup");
 }
 
 int aarmvs_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t stream) {

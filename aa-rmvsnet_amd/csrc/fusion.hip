@@ -10,11 +10,14 @@
 // float maps (coordinates rounded to 1/32 px, table weights, left-to-right float32 sum,
 // out-of-image taps 0), relative depth differences and depth sums in float32.
 // Algorithmic bytes per reference pixel: depth + confidence (8) + one depth read per source
-// view (4 nsrc) + three masks and the float64 average (11).
+// view (4 nsrc) + three masks and the float64 average (11).  The de-duplicating instantiation
+// (aarmvs_fusion_filter_dedup) adds the reference view's used byte and the emit mask (2) and one
+// byte store per final pixel and consistent source view.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "aarmvs_internal.h"
 
@@ -31,6 +34,13 @@ struct FusionArgs {
   unsigned char* geo_mask;
   unsigned char* final_mask;
   double* depth_avg;
+};
+
+// the de-duplicating instantiation's arguments: the plain ones, then aarmvs_fusion_dedup_args
+struct FusionDedupArgs : FusionArgs {
+  const unsigned char* used_ref;
+  unsigned char* used_src[AARMVS_MAX_FUSION_SRC];
+  unsigned char* emit_mask;
 };
 
 // rows r of a row-major float32 matrix (columns cols) times a float64 vector, as numpy's
@@ -68,12 +78,26 @@ __device__ __forceinline__ float remap_linear(const float* __restrict__ src, int
   return r;
 }
 
-__global__ void __launch_bounds__(256) fusion_filter_kernel(FusionArgs a) {
+// DEDUP = false is the plain filter.  DEDUP = true (the visibility de-duplication,
+// include/aarmvs.h): per source view, the pixel nearest to the float32 coordinates remap_linear
+// is given -- or -1 where the i = 10 mask fails or that pixel lies outside the image -- waits in
+// the thread's own LDS slots (an array indexed by the source view must not live in registers)
+// until final is known; then emit = final && !used_ref is written, and a final pixel sets those
+// pixels in the source views' used maps.  used_ref is only read and the used_src maps are only
+// written here, and every writer stores 1.
+template <bool DEDUP>
+__global__ void __launch_bounds__(256)
+fusion_filter_kernel(std::conditional_t<DEDUP, FusionDedupArgs, FusionArgs> a) {
   const int H = a.H, W = a.W, nsrc = a.nsrc, n = nsrc + 1;
   // cams: invK_ref[9], K_ref[9], then per source view K[9], invK[9], M1[12] = (E_src
   // inv(E_ref))[:3], M2[12] = (E_ref inv(E_src))[:3]
   const float* invK_ref = a.cams;
   const float* K_ref = a.cams + 9;
+  [[maybe_unused]] int* marks = nullptr;   // [source view][thread]: nobody reads another's slot
+  if constexpr (DEDUP) {
+    __shared__ int mark_slots[AARMVS_MAX_FUSION_SRC * 256];
+    marks = mark_slots + threadIdx.x;
+  }
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < H * W; p += gridDim.x * blockDim.x) {
     const int y = p / W, x = p - y * W;
     const float dref = a.ref_depth[p];
@@ -112,6 +136,12 @@ __global__ void __launch_bounds__(256) fusion_filter_kernel(FusionArgs a) {
       }
       if (!m) depth_rep = 0.0f;   // depth_reprojected[~mask] = 0 (mask: i = 10)
       geo_sum += m ? 1 : 0;
+      if constexpr (DEDUP) {
+        // nearest pixel, ties to even; NaN and +-inf fail the comparisons
+        const double X = (double)rintf((float)xsrc), Y = (double)rintf((float)ysrc);
+        const bool inside = X >= 0.0 && X < (double)W && Y >= 0.0 && Y < (double)H;
+        marks[v * 256] = (m && inside) ? (int)Y * W + (int)X : -1;
+      }
       depth_sum = __fadd_rn(depth_sum, depth_rep);
     }
     // filter_depth (:207-220)
@@ -124,11 +154,25 @@ __global__ void __launch_bounds__(256) fusion_filter_kernel(FusionArgs a) {
     a.geo_mask[p] = geo ? 1 : 0;
     a.final_mask[p] = (photo && geo) ? 1 : 0;
     a.depth_avg[p] = (double)__fadd_rn(depth_sum, dref) / (double)(geo_sum + 1);
+    if constexpr (DEDUP) {
+      const bool fin = photo && geo;
+      const bool used = a.used_ref != nullptr && a.used_ref[p] != 0;
+      a.emit_mask[p] = (fin && !used) ? 1 : 0;
+      if (!fin) continue;
+      for (int v = 0; v < nsrc; ++v) {
+        unsigned char* mark = a.used_src[v];
+        const int at = marks[v * 256];
+        if (at >= 0 && mark != nullptr) mark[at] = 1;
+      }
+    }
   }
 }
 
-hipError_t launch_fusion_filter(const aarmvs_fusion_args* in, hipStream_t s) {
-  FusionArgs a{};
+static int fusion_blocks(int H, int W) {
+  return std::max(1, std::min((H * W + 255) / 256, 65535));
+}
+
+static void fill_fusion_args(FusionArgs& a, const aarmvs_fusion_args* in) {
   a.H = in->H;
   a.W = in->W;
   a.nsrc = in->nsrc;
@@ -141,10 +185,26 @@ hipError_t launch_fusion_filter(const aarmvs_fusion_args* in, hipStream_t s) {
   a.geo_mask = in->geo_mask;
   a.final_mask = in->final_mask;
   a.depth_avg = in->depth_avg;
-  const int HW = a.H * a.W;
-  const int blocks = std::max(1, std::min((HW + 255) / 256, 65535));
+}
+
+hipError_t launch_fusion_filter(const aarmvs_fusion_args* in, hipStream_t s) {
+  FusionArgs a{};
+  fill_fusion_args(a, in);
   ProfScope ps(s, K_FUSION);
-  hipLaunchKernelGGL(fusion_filter_kernel, dim3(blocks), dim3(256), 0, s, a);
+  hipLaunchKernelGGL(fusion_filter_kernel<false>, dim3(fusion_blocks(a.H, a.W)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// (timed under the plain filter's profile id: the list of kernel names is fixed)
+hipError_t launch_fusion_filter_dedup(const aarmvs_fusion_args* in, const aarmvs_fusion_dedup_args* d,
+                                      hipStream_t s) {
+  FusionDedupArgs a{};
+  fill_fusion_args(a, in);
+  a.used_ref = d->used_ref;
+  for (int v = 0; v < in->nsrc; ++v) a.used_src[v] = d->used_src[v];
+  a.emit_mask = d->emit_mask;
+  ProfScope ps(s, K_FUSION);
+  hipLaunchKernelGGL(fusion_filter_kernel<true>, dim3(fusion_blocks(a.H, a.W)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -517,6 +517,46 @@ typedef struct aarmvs_fusion_args {
 int aarmvs_fusion_filter(const aarmvs_fusion_args* args, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Opt-in visibility de-duplication of the fused cloud (not in the reference; the used-pixel
+ * marking of Gipuma-style fusion).  The reference emits a point for every final pixel of every
+ * reference view, so a surface patch seen consistently from k views lands in the cloud about k
+ * times.  With this mode a scan keeps one USED MAP per view: uint8 [H,W] on the device, in the
+ * pixel grid of that view's depth map, zero at the start of the scan (the caller allocates and
+ * clears it).  Reference views are processed in pair-file order.  For reference view r with
+ * source views s_0 .. s_{nsrc-1}, with aarmvs_fusion_filter's arithmetic unchanged:
+ *   final(p)     the final mask;
+ *   m_v(p)       per source view, the i = 10 geometric mask (the one that zeroes the reprojected
+ *                depth);
+ *   x_v, y_v     per source view, the float32 source coordinates that the depth map is sampled at.
+ *   emit(p) = final(p) && used[r][p] == 0
+ *   for every p with final(p) -- emitted or not, so that coverage propagates through views that
+ *   do not list each other -- and every v with m_v(p):
+ *       X = rintf(x_v), Y = rintf(y_v)   (nearest pixel, ties to even)
+ *       if 0 <= X < W and 0 <= Y < H:  used[s_v][Y W + X] = 1
+ *   (non-finite and out-of-image coordinates mark nothing).
+ * The view's points are the pixels of emit_mask instead of final_mask (pass it to
+ * aarmvs_fusion_points); the averaged depth, the back-projection and the colour are unchanged, and
+ * photo_mask, geo_mask, final_mask and depth_avg are bit-identical to aarmvs_fusion_filter's.
+ * Deterministic: within a call used_ref is only read and the used_src maps are only written, every
+ * writer stores the same byte (plain stores, no atomics), and emit depends only on the marks of
+ * earlier calls -- so THE CALLS OF ONE SCAN MUST BE ORDERED ON ONE STREAM (or otherwise ordered by
+ * the caller), in pair-file order.
+ * used_ref NULL: nothing used yet (emit = final).  used_src[v] NULL: that view is not marked.
+ * AARMVS_ERR_INVALID, before any launch: emit_mask NULL; used_ref equal to a used_src[v] (a view is
+ * not its own source view); emit_mask equal to photo_mask, geo_mask or final_mask; and everything
+ * aarmvs_fusion_filter rejects.  dedup == NULL is aarmvs_fusion_filter(args, stream).
+ * The launch is timed under the profiler's "fusion" id (the list of kernel names is fixed).
+ * The effect on DTU and Tanks and Temples scores is not measured (no datasets here).
+ * ------------------------------------------------------------------------- */
+typedef struct aarmvs_fusion_dedup_args {
+  const unsigned char* used_ref;                    /* [H,W] or NULL (nothing used yet: emit = final) */
+  unsigned char* used_src[AARMVS_MAX_FUSION_SRC];   /* [H,W] each; NULL: that view is not marked      */
+  unsigned char* emit_mask;                         /* [H,W] out, required                            */
+} aarmvs_fusion_dedup_args;
+int aarmvs_fusion_filter_dedup(const aarmvs_fusion_args* args, const aarmvs_fusion_dedup_args* dedup,
+                               hipStream_t stream);
+
+/* ---------------------------------------------------------------------------
  * One level of OpenCV's 5x5 Gaussian pyramid (cv2.pyrDown, imgproc/src/pyramids.cpp, the
  * scalar float path), which fusion_padding.py:166 applies to the reference image: `src`
  * device float32 [H,W,C] interleaved, C = 1 or 3; `dst` device [(H+1)/2, (W+1)/2, C].
