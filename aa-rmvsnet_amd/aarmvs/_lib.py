@@ -133,6 +133,24 @@ class FusionPointsArgs(ctypes.Structure):
     ]
 
 
+MAX_NORMAL_RADIUS = 3
+FUSION_NORMAL_CAM_FLOATS = 25
+
+
+class FusionNormalsArgs(ctypes.Structure):
+    """Mirror of ``aarmvs_fusion_normals_args``."""
+    _fields_ = [
+        ("H", c_int), ("W", c_int),
+        ("depth", c_void_p),
+        ("valid", c_void_p),
+        ("cams", c_void_p),
+        ("radius", c_int), ("min_count", c_int),
+        ("max_rel_jump", ctypes.c_float),
+        ("normal", c_void_p),
+        ("has_normal", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "aarmvs_last_error": (c_char_p, []),
@@ -190,6 +208,8 @@ SIGNATURES = {
     "aarmvs_pyr_down": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "aarmvs_fusion_points_workspace_bytes": (c_size_t, [c_int, c_int]),
     "aarmvs_fusion_points": (c_int, [ctypes.POINTER(FusionPointsArgs), c_void_p]),
+    "aarmvs_fusion_normals": (c_int, [ctypes.POINTER(FusionNormalsArgs), c_void_p]),
+    "aarmvs_fusion_points_normals": (c_int, [ctypes.POINTER(FusionPointsArgs), c_void_p, c_void_p, c_void_p]),
     "aarmvs_evidential_epilogue": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p,
                                            c_void_p, c_void_p]),
     "aarmvs_evidential_epilogue_backward": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int,

@@ -26,6 +26,15 @@ marks the pixel it projects to in every source view it is consistent with, and a
 only its final pixels that are not marked, so a surface patch seen from k views is emitted about
 once instead of k times.  Off (the default) nothing changes.  Its effect on DTU and Tanks and
 Temples scores is not measured.
+
+Opt-in, beyond the reference: per-point normals (``--normals``, ``normals=True`` or a dict of
+``radius`` / ``max_rel_jump`` / ``min_count`` on both drivers and on ``fuse_views``;
+``estimate_normals`` per view, ``aarmvs_fusion_normals``).  A view's normal map is a least-squares fit
+of 1/d = a x + b y + c over a window of its averaged depth map, restricted to the view's final mask
+and to neighbours within ``max_rel_jump`` of the centre's depth; the normals face the camera, travel
+with the kept pixels (``fuse_points_normals_gpu``, ``aarmvs_fusion_points_normals``) and go to the
+PLY as nx ny nz.  Off (the default) nothing changes.  The effect on meshes of DTU and Tanks and
+Temples clouds is not measured.
 """
 from __future__ import annotations
 
@@ -213,7 +222,8 @@ def resize_linear(img, width, height):
 
 
 def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="cuda",
-                 depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR, dedup=False):
+                 depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR, dedup=False, normals=None,
+                 require_normal=False):
     """fusion.py:135-273 for one scan: for every (ref_view, src_views) of pair.txt with an
     estimated depth map, the geometric / photometric filtering on the GPU
     (``filter_depth_core``), the three mask PNGs under out_folder/mask, and the kept pixels'
@@ -224,8 +234,14 @@ def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="
     confidence_window_0).  ``dedup``: the opt-in visibility de-duplication
     (``filter_depth_dedup``): every view's depth map (read once) and used map stay on the GPU for
     the whole scan, the points are those of the emit mask, and mask/{view}_emit.png is written
-    beside the other three."""
-    vertexs, vertex_colors = [], []
+    beside the other three.  ``normals`` (None / False, True, or a dict of ``radius`` /
+    ``max_rel_jump`` / ``min_count``): the opt-in per-point normals (``estimate_normals`` on the
+    averaged depth and the final mask), written to the PLY as nx ny nz; ``require_normal`` (with
+    ``normals``): only the pixels that have a normal are extracted."""
+    vertexs, vertex_colors, vertex_normals = [], [], []
+    nparams = normal_params(normals)
+    if require_normal and nparams is None:
+        raise AarmvsError("aarmvs: require_normal needs normals")
     dev = torch.device(device)
     depth_file = os.path.join(out_folder, depth_dir, "{:0>8}.pfm")
     cache, used = {}, _UsedMaps()
@@ -268,6 +284,8 @@ def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="
                 torch.from_numpy(np.ascontiguousarray(ref_depth_est)).to(dev),
                 torch.from_numpy(np.ascontiguousarray(confidence)).to(dev), ref_cam, src_depths, src_cams,
                 photo_threshold)
+        if nparams is not None:
+            nmap, has = estimate_normals(avg, final, ref_cam, **nparams)
         photo, geo, final = (m.cpu().numpy() for m in (photo, geo, final))
         os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
         save_mask(os.path.join(out_folder, "mask/{:0>8}_photo.png".format(ref_view)), photo)
@@ -278,14 +296,15 @@ def filter_depth(scan_folder, out_folder, plyfilename, photo_threshold, device="
         if dedup:
             save_mask(os.path.join(out_folder, "mask/{:0>8}_emit.png".format(ref_view)), emit)
             print("  emit-mask:{}".format(emit.mean()))
-        xyz, rgb = fuse_points(avg.cpu().numpy(), emit if dedup else final, ref_cam, ref_img)
+        keep = emit if dedup else final
+        if nparams is not None:
+            if require_normal:
+                keep = np.logical_and(keep, has.cpu().numpy())
+            vertex_normals.append(nmap.cpu().numpy()[keep])
+        xyz, rgb = fuse_points(avg.cpu().numpy(), keep, ref_cam, ref_img)
         vertexs.append(xyz)
         vertex_colors.append(rgb)
-    xyz = np.concatenate(vertexs, axis=0) if vertexs else np.zeros((0, 3), np.float32)
-    rgb = np.concatenate(vertex_colors, axis=0) if vertex_colors else np.zeros((0, 3), np.uint8)
-    write_ply(plyfilename, xyz, rgb)
-    print("saving the final model to", plyfilename)
-    return xyz.shape[0]
+    return _write_scan_ply(plyfilename, vertexs, vertex_colors, vertex_normals if nparams is not None else None)
 
 
 # ---------------------------------------------------------------------------------
@@ -318,11 +337,13 @@ def pack_point_cameras(ref_cam) -> np.ndarray:
                                 .astype(np.float32))
 
 
-def fuse_points_into(depth_avg, final_mask, ref_cam, ref_img, xyz, rgb) -> torch.Tensor:
+def fuse_points_into(depth_avg, final_mask, ref_cam, ref_img, xyz, rgb, *, normal_map=None, nrm=None) -> torch.Tensor:
     """The kept pixels' world points into the caller's buffers: xyz float32 [capacity,3], rgb
     uint8 [capacity,3] (None if and only if ref_img is), in pixel order; points past the
     capacity are dropped.  Returns the number of kept pixels as a CUDA int64 [1] tensor,
-    without waiting for the device."""
+    without waiting for the device.  ``normal_map`` (CUDA float32 [H,W,3], ``estimate_normals``)
+    and ``nrm`` (float32 [capacity,3]), both or neither: the kept pixels' normals go to ``nrm``
+    (``aarmvs_fusion_points_normals``)."""
     if not (isinstance(depth_avg, torch.Tensor) and depth_avg.is_cuda and depth_avg.dtype == torch.float64
             and depth_avg.dim() == 2):
         raise AarmvsError("aarmvs: fuse_points_gpu needs the averaged depth as a CUDA float64 [H,W] tensor")
@@ -346,6 +367,19 @@ def fuse_points_into(depth_avg, final_mask, ref_cam, ref_img, xyz, rgb) -> torch
             raise AarmvsError(f"aarmvs: fuse_points_gpu: {what} must be a contiguous CUDA [n,3] tensor")
     if rgb is not None and rgb.shape[0] != xyz.shape[0]:
         raise AarmvsError("aarmvs: fuse_points_gpu: xyz and rgb differ in capacity")
+    if (normal_map is None) != (nrm is None):
+        raise AarmvsError("aarmvs: fuse_points_gpu: normals out need a normal map, and a normal map normals out")
+    if normal_map is not None:
+        if not (isinstance(normal_map, torch.Tensor) and normal_map.device == dev
+                and normal_map.dtype == torch.float32 and tuple(normal_map.shape) == (H, W, 3)):
+            raise AarmvsError("aarmvs: fuse_points_gpu needs the normal map as a CUDA float32 [H,W,3] tensor "
+                              "of the depth map's size")
+        normal_map = normal_map.contiguous()
+        if not (isinstance(nrm, torch.Tensor) and nrm.device == dev and nrm.dtype == torch.float32
+                and nrm.dim() == 2 and nrm.shape[1] == 3 and nrm.is_contiguous()):
+            raise AarmvsError("aarmvs: fuse_points_gpu: nrm must be a contiguous CUDA [n,3] tensor")
+        if nrm.shape[0] != xyz.shape[0]:
+            raise AarmvsError("aarmvs: fuse_points_gpu: xyz and nrm differ in capacity")
     depth_avg, final_mask = depth_avg.contiguous(), final_mask.contiguous()
     cams = pack_point_cameras(ref_cam)
     count = torch.empty(1, dtype=torch.int64, device=dev)
@@ -360,8 +394,13 @@ def fuse_points_into(depth_avg, final_mask, ref_cam, ref_img, xyz, rgb) -> torch
     a.capacity = xyz.shape[0]
     a.count, a.workspace = count.data_ptr(), work.data_ptr()
     with torch.cuda.device(dev):
-        check(lib().aarmvs_fusion_points(ctypes.byref(a), torch.cuda.current_stream().cuda_stream),
-              "fusion_points")
+        if normal_map is None:
+            check(lib().aarmvs_fusion_points(ctypes.byref(a), torch.cuda.current_stream().cuda_stream),
+                  "fusion_points")
+        else:
+            check(lib().aarmvs_fusion_points_normals(ctypes.byref(a), normal_map.data_ptr(), nrm.data_ptr(),
+                                                     torch.cuda.current_stream().cuda_stream),
+                  "fusion_points_normals")
     return count
 
 
@@ -378,6 +417,99 @@ def fuse_points_gpu(depth_avg, final_mask, ref_cam, ref_img=None):
     return xyz[:n], (None if rgb is None else rgb[:n])
 
 
+# ---------------------------------------------------------------------------------
+# opt-in per-point normals (not in the reference; include/aarmvs.h)
+# ---------------------------------------------------------------------------------
+NORMAL_DEFAULTS = dict(radius=2, max_rel_jump=0.01, min_count=3)
+
+
+def normal_params(normals):
+    """The ``normals`` argument of ``fuse_views`` and the drivers as ``estimate_normals``' keywords:
+    None for False / None, the defaults for True, a dict of ``radius`` / ``max_rel_jump`` /
+    ``min_count`` over the defaults."""
+    if normals is None or normals is False:
+        return None
+    if normals is True:
+        return dict(NORMAL_DEFAULTS)
+    if not isinstance(normals, dict) or set(normals) - set(NORMAL_DEFAULTS):
+        raise AarmvsError(f"aarmvs: normals must be a bool or a dict of {sorted(NORMAL_DEFAULTS)}, got {normals!r}")
+    return {**NORMAL_DEFAULTS, **normals}
+
+
+def pack_normal_cameras(ref_cam) -> np.ndarray:
+    """K 3x3 (of the depth map's pixel grid) then inv(E) 4x4 as numpy forms it in float32, packed for
+    ``aarmvs_fusion_normals``."""
+    K, E = (np.asarray(m, np.float32) for m in ref_cam)
+    out = np.ascontiguousarray(np.concatenate([K.ravel(), np.linalg.inv(E).ravel()]).astype(np.float32))
+    assert out.size == _lib.FUSION_NORMAL_CAM_FLOATS
+    return out
+
+
+def estimate_normals(depth_avg, valid, ref_cam, radius=2, max_rel_jump=0.01, min_count=3):
+    """Per-pixel world normals of a view's averaged depth map (``aarmvs_fusion_normals``,
+    include/aarmvs.h): a float64 least-squares fit of 1/d = a x + b y + c over the (2 radius + 1)^2
+    window's usable pixels -- those of ``valid`` with a finite depth > 0 within ``max_rel_jump``
+    (relative) of the centre's -- needing ``min_count`` of them, not collinear.  ``depth_avg``: CUDA
+    float64 [H,W]; ``valid``: CUDA bool / uint8 [H,W]; ``ref_cam``: (K, E) of the depth map's grid.
+    ``max_rel_jump``'s default is the reference's relative depth threshold in
+    check_geometric_consistency; ``min_count``'s is every solvable fit.  Returns (normal float32
+    [H,W,3]: unit, facing the camera, (0,0,0) where there is none; has bool [H,W]) as CUDA tensors."""
+    if not (isinstance(depth_avg, torch.Tensor) and depth_avg.is_cuda and depth_avg.dtype == torch.float64
+            and depth_avg.dim() == 2):
+        raise AarmvsError("aarmvs: estimate_normals needs the averaged depth as a CUDA float64 [H,W] tensor")
+    dev = depth_avg.device
+    if not (isinstance(valid, torch.Tensor) and valid.device == dev and valid.dtype in (torch.bool, torch.uint8)
+            and valid.shape == depth_avg.shape):
+        raise AarmvsError("aarmvs: estimate_normals needs the mask as a CUDA bool / uint8 [H,W] tensor of the "
+                          "depth map's size")
+    H, W = depth_avg.shape
+    depth_avg, valid = depth_avg.contiguous(), valid.contiguous()
+    cams = pack_normal_cameras(ref_cam)
+    normal = torch.empty(H, W, 3, dtype=torch.float32, device=dev)
+    has = torch.empty(H, W, dtype=torch.uint8, device=dev)
+    a = _lib.FusionNormalsArgs()
+    a.H, a.W = H, W
+    a.depth, a.valid = depth_avg.data_ptr(), valid.data_ptr()
+    a.cams = cams.ctypes.data
+    a.radius, a.min_count = int(radius), int(min_count)
+    a.max_rel_jump = float(max_rel_jump)
+    a.normal, a.has_normal = normal.data_ptr(), has.data_ptr()
+    with torch.cuda.device(dev):
+        check(lib().aarmvs_fusion_normals(ctypes.byref(a), torch.cuda.current_stream().cuda_stream),
+              "fusion_normals")
+    return normal, has.bool()
+
+
+def fuse_points_normals_gpu(depth_avg, final_mask, ref_cam, ref_img, normal_map):
+    """``fuse_points_gpu`` with the kept pixels' normals (``aarmvs_fusion_points_normals``): (xyz
+    float32 [n,3], rgb uint8 [n,3] or None, nrm float32 [n,3]), ``nrm`` = ``normal_map[mask]`` in
+    pixel order, lined up with ``xyz`` and ``rgb``, which are ``fuse_points_gpu``'s bit for bit."""
+    if not (isinstance(depth_avg, torch.Tensor) and depth_avg.is_cuda and depth_avg.dim() == 2):
+        raise AarmvsError("aarmvs: fuse_points_gpu needs the averaged depth as a CUDA float64 [H,W] tensor")
+    (H, W), dev = depth_avg.shape, depth_avg.device
+    xyz = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
+    nrm = torch.empty(H * W, 3, dtype=torch.float32, device=dev)
+    rgb = None if ref_img is None else torch.empty(H * W, 3, dtype=torch.uint8, device=dev)
+    n = int(fuse_points_into(depth_avg, final_mask, ref_cam, ref_img, xyz, rgb, normal_map=normal_map,
+                             nrm=nrm).item())
+    return xyz[:n], (None if rgb is None else rgb[:n]), nrm[:n]
+
+
+def _write_scan_ply(plyfilename, vertexs, vertex_colors, vertex_normals=None):
+    """The drivers' last step: the views' points, colours and (with normals) normals, concatenated,
+    to the PLY.  Returns the number of points."""
+    xyz = np.concatenate(vertexs, axis=0) if vertexs else np.zeros((0, 3), np.float32)
+    rgb = np.concatenate(vertex_colors, axis=0) if vertex_colors else np.zeros((0, 3), np.uint8)
+    if vertex_normals is None:
+        write_ply(plyfilename, xyz, rgb)
+    else:
+        nrm = np.concatenate(vertex_normals, axis=0) if vertex_normals else np.zeros((0, 3), np.float32)
+        write_ply(plyfilename, xyz, rgb, nrm)
+        print("points without a normal: {} of {}".format(int((~nrm.any(axis=1)).sum()), nrm.shape[0]))
+    print("saving the final model to", plyfilename)
+    return xyz.shape[0]
+
+
 class _UsedMaps:
     """A scan's used maps (the visibility de-duplication's state): one zeroed CUDA uint8 map per
     view id, allocated when the view is first a reference or a source view."""
@@ -391,7 +523,8 @@ class _UsedMaps:
         return self.maps[view]
 
 
-def fuse_views(pairs, depths, confidences, cams, images=None, photo_threshold=0.35, dedup=False):
+def fuse_views(pairs, depths, confidences, cams, images=None, photo_threshold=0.35, dedup=False, normals=False,
+               require_normal=False):
     """Filter and fuse a scan held in memory.  ``pairs``: [(ref_view, [src_view, ...]), ...] in
     pair-file order; ``depths`` / ``confidences``: {view: CUDA float32 [H,W]}; ``cams``: {view: (K,
     E)}; ``images``: {view: CUDA float32 [H,W,3] in [0,1]} or None.  Reference views absent from
@@ -401,9 +534,19 @@ def fuse_views(pairs, depths, confidences, cams, images=None, photo_threshold=0.
     marked), then ``fuse_points_gpu`` on the final / emit mask.  Returns a dict: ``xyz`` float32
     [n,3] and ``rgb`` uint8 [n,3] (None without images) CUDA tensors, ``masks`` {view: {"photo",
     "geo", "final"(, "emit"): bool [H,W]}}, ``avg`` {view: float64 [H,W]}, ``counts`` {view: points
-    emitted} and, with ``dedup``, ``used`` {view: uint8 [H,W]} after the scan."""
+    emitted} and, with ``dedup``, ``used`` {view: uint8 [H,W]} after the scan.  ``normals`` (True, or
+    a dict of ``radius`` / ``max_rel_jump`` / ``min_count``): per view ``estimate_normals`` on the
+    averaged depth and the FINAL mask -- also under ``dedup``: the emit mask only selects what is
+    extracted, a de-duplicated view keeps its neighbours for the fit -- and the dict gains
+    ``normals`` float32 [n,3] lined up with ``xyz``, ``normal_maps`` {view: float32 [H,W,3]} and
+    ``has_normal`` {view: bool [H,W]}; everything else is bit for bit what it is without.
+    ``require_normal`` (with ``normals``): extract only the pixels that have a normal."""
     used = _UsedMaps()
     masks, avgs, counts, verts, cols = {}, {}, {}, [], []
+    nparams = normal_params(normals)
+    if require_normal and nparams is None:
+        raise AarmvsError("aarmvs: require_normal needs normals")
+    nmaps, has_maps, nrms = {}, {}, []
     dev = None
     for ref_view, src_views in pairs:
         if ref_view not in depths:
@@ -422,7 +565,15 @@ def fuse_views(pairs, depths, confidences, cams, images=None, photo_threshold=0.
                                                        src_depths, src_cams, photo_threshold)
             emit = final
             masks[ref_view] = dict(photo=photo, geo=geo, final=final)
-        xyz, rgb = fuse_points_gpu(avg, emit, cams[ref_view], None if images is None else images[ref_view])
+        img = None if images is None else images[ref_view]
+        if nparams is None:
+            xyz, rgb = fuse_points_gpu(avg, emit, cams[ref_view], img)
+        else:
+            nmap, has = estimate_normals(avg, final, cams[ref_view], **nparams)
+            nmaps[ref_view], has_maps[ref_view] = nmap, has
+            xyz, rgb, nrm = fuse_points_normals_gpu(avg, emit & has if require_normal else emit, cams[ref_view],
+                                                    img, nmap)
+            nrms.append(nrm)
         avgs[ref_view], counts[ref_view] = avg, int(xyz.shape[0])
         verts.append(xyz)
         cols.append(rgb)
@@ -435,6 +586,9 @@ def fuse_views(pairs, depths, confidences, cams, images=None, photo_threshold=0.
     out = dict(xyz=xyz, rgb=rgb, masks=masks, avg=avgs, counts=counts)
     if dedup:
         out["used"] = used.maps
+    if nparams is not None:
+        out["normals"] = torch.cat(nrms) if nrms else torch.zeros(0, 3, dtype=torch.float32, device=dev)
+        out["normal_maps"], out["has_normal"] = nmaps, has_maps
     return out
 
 
@@ -447,7 +601,8 @@ def read_camera_parameters_tnt(filename):
 
 
 def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, device="cuda",
-                     depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR, dedup=False):
+                     depth_dir=DEFAULT_DEPTH_DIR, conf_dir=DEFAULT_CONF_DIR, dedup=False, normals=None,
+                     require_normal=False):
     """fusion_padding.py:137-266 for one scan.  Per reference view of pair.txt: the image goes
     to the GPU and through ``pyr_down``; rows [2:-2] are cropped from the reference and source
     depth maps and the confidence map (the padding loader's extra rows); ``filter_depth_core``
@@ -457,8 +612,13 @@ def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, 
     back to the host.  Writes plyfilename and returns the number of points.  A reference view
     without a depth map is skipped (the reference stops with an error there).  ``depth_dir`` /
     ``conf_dir``, ``dedup``: as for ``filter_depth`` (the cropped depth maps stay on the GPU for the
-    whole scan either way; with ``dedup`` the used maps do too)."""
-    vertexs, vertex_colors = [], []
+    whole scan either way; with ``dedup`` the used maps do too).  ``normals``, ``require_normal``: as
+    for ``filter_depth``; the fit runs on the cropped half-size maps with the halved intrinsics, the
+    grid the points come from."""
+    vertexs, vertex_colors, vertex_normals = [], [], []
+    nparams = normal_params(normals)
+    if require_normal and nparams is None:
+        raise AarmvsError("aarmvs: require_normal needs normals")
     dev = torch.device(device)
     cam_file = os.path.join(scan_folder, "cams/{:0>8}_cam.txt")
     depth_file = os.path.join(out_folder, depth_dir, "{:0>8}.pfm")
@@ -489,12 +649,19 @@ def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, 
             photo, geo, final, emit, avg = filter_depth_dedup(
                 ref_depth_est, confidence, ref_cam, [depth_of(v) for v in src_views], src_cams, photo_threshold,
                 used.of(ref_view, ref_depth_est), [used.of(v, depth_of(v)) for v in src_views])
-            xyz, rgb = fuse_points_gpu(avg, emit, ref_cam, ref_img)
+            keep = emit
             emit = emit.cpu().numpy()
         else:
             photo, geo, final, avg = filter_depth_core(ref_depth_est, confidence, ref_cam,
                                                        [depth_of(v) for v in src_views], src_cams, photo_threshold)
-            xyz, rgb = fuse_points_gpu(avg, final, ref_cam, ref_img)
+            keep = final
+        if nparams is None:
+            xyz, rgb = fuse_points_gpu(avg, keep, ref_cam, ref_img)
+        else:
+            nmap, has = estimate_normals(avg, final, ref_cam, **nparams)
+            xyz, rgb, nrm = fuse_points_normals_gpu(avg, keep & has if require_normal else keep, ref_cam, ref_img,
+                                                    nmap)
+            vertex_normals.append(nrm.cpu().numpy())
         photo, geo, final = (m.cpu().numpy() for m in (photo, geo, final))
         os.makedirs(os.path.join(out_folder, "mask"), exist_ok=True)
         save_mask(os.path.join(out_folder, "mask/{:0>8}_photo.png".format(ref_view)), photo)
@@ -507,11 +674,7 @@ def filter_depth_tnt(scan_folder, out_folder, plyfilename, photo_threshold=0.3, 
             print("  emit-mask:{}".format(emit.mean()))
         vertexs.append(xyz.cpu().numpy())
         vertex_colors.append(rgb.cpu().numpy())
-    xyz = np.concatenate(vertexs, axis=0) if vertexs else np.zeros((0, 3), np.float32)
-    rgb = np.concatenate(vertex_colors, axis=0) if vertex_colors else np.zeros((0, 3), np.uint8)
-    write_ply(plyfilename, xyz, rgb)
-    print("saving the final model to", plyfilename)
-    return xyz.shape[0]
+    return _write_scan_ply(plyfilename, vertexs, vertex_colors, vertex_normals if nparams is not None else None)
 
 
 # ---------------------------------------------------------------------------------
@@ -557,15 +720,23 @@ def read_pair_file(filename):
     return data
 
 
-def write_ply(filename, xyz, rgb=None):
-    """Binary little-endian PLY of float32 x, y, z (+ uint8 red, green, blue) vertices."""
+def write_ply(filename, xyz, rgb=None, normals=None):
+    """Binary little-endian PLY of float32 x, y, z (+ float32 nx, ny, nz) (+ uint8 red, green, blue)
+    vertices, the property order that MeshLab, Open3D and COLMAP read."""
     xyz = np.asarray(xyz, np.float32)
     n = xyz.shape[0]
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals is not None:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
     if rgb is not None:
         fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
     v = np.empty(n, dtype=fields)
     v["x"], v["y"], v["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if normals is not None:
+        normals = np.asarray(normals, np.float32)
+        if normals.shape != xyz.shape:
+            raise ValueError("write_ply: normals must have xyz's shape")
+        v["nx"], v["ny"], v["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     if rgb is not None:
         rgb = np.asarray(rgb, np.uint8)
         v["red"], v["green"], v["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
@@ -600,6 +771,17 @@ def build_parser():
     p.add_argument("--dedup", action="store_true",
                    help="visibility de-duplication: a view emits only the final pixels that no earlier view's "
                         "consistent match marked (off: the reference's cloud; DESIGN.md §4b)")
+    p.add_argument("--normals", action="store_true",
+                   help="per-point normals (nx ny nz in the PLY) from a window fit of every view's averaged depth "
+                        "(off: the reference's cloud; DESIGN.md §4c)")
+    p.add_argument("--normal_radius", type=int, choices=[1, 2, 3], default=NORMAL_DEFAULTS["radius"],
+                   help="--normals: the fit's window is (2 r + 1)^2 pixels")
+    p.add_argument("--normal_max_rel_jump", type=float, default=NORMAL_DEFAULTS["max_rel_jump"],
+                   help="--normals: a neighbour takes part when its depth is within this (relative) of the centre's")
+    p.add_argument("--normal_min_count", type=int, default=NORMAL_DEFAULTS["min_count"],
+                   help="--normals: usable pixels a fit needs (3 .. (2 r + 1)^2)")
+    p.add_argument("--require_normal", action="store_true",
+                   help="--normals: emit only the pixels that have a normal (off: the point set does not change)")
     p.add_argument("--device", default="cuda")
     return p
 
@@ -608,6 +790,8 @@ def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     if args.photo_threshold is None:
         args.photo_threshold = DEFAULT_PHOTO_THRESHOLD[args.test_dataset]
+    if args.require_normal and not args.normals:
+        build_parser().error("--require_normal needs --normals")
     return args
 
 
@@ -628,13 +812,18 @@ def main(argv=None):
         scan_folder = os.path.join(args.testpath, scan)
         out_folder = os.path.join(args.outdir, scan)
         ply = ply_path(args.outdir, scan, args.test_dataset)
-        # (the folders and --dedup are passed on only when they are not the defaults: the default
+        # (the folders, --dedup and --normals are passed on only when they are not the defaults: the default
         # call is the five-argument one it has always been)
         dirs = {}
         if (args.depth_dir, args.conf_dir) != (DEFAULT_DEPTH_DIR, DEFAULT_CONF_DIR):
             dirs = dict(depth_dir=args.depth_dir, conf_dir=args.conf_dir)
         if args.dedup:
             dirs["dedup"] = True
+        if args.normals:
+            dirs["normals"] = dict(radius=args.normal_radius, max_rel_jump=args.normal_max_rel_jump,
+                                   min_count=args.normal_min_count)
+            if args.require_normal:
+                dirs["require_normal"] = True
         if args.test_dataset == "tnt":
             filter_depth_tnt(scan_folder, out_folder, ply, args.photo_threshold, args.device, **dirs)
         else:

@@ -161,7 +161,11 @@ hipError_t launch_fusion_filter_dedup(const aarmvs_fusion_args* a, const aarmvs_
 // reference view's kept pixels (fusion.hip)
 hipError_t launch_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t s);
 size_t fusion_points_workspace_bytes(int H, int W);
-hipError_t launch_fusion_points(const aarmvs_fusion_points_args* a, hipStream_t s);
+// (normal_map != nullptr: the kept pixels' normals go to nxyz as well)
+hipError_t launch_fusion_points(const aarmvs_fusion_points_args* a, const float* normal_map, float* nxyz,
+                                hipStream_t s);
+// per-pixel normals of a view's averaged depth map (fusion.hip)
+hipError_t launch_fusion_normals(const aarmvs_fusion_normals_args* a, hipStream_t s);
 // xmax (optional, to_nhwc only): atomic max of |in| as float bits
 hipError_t launch_layout(const float* in, float* out, int B, int C, int HW, bool to_nhwc,
                          hipStream_t s, unsigned* xmax = nullptr);

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -1235,7 +1237,7 @@ size_t aarmvs_fusion_points_workspace_bytes(int H, int W) {
   return fusion_points_workspace_bytes(H, W);
 }
 
-int aarmvs_fusion_points(const aarmvs_fusion_points_args* a, hipStream_t stream) {
+static int fusion_points_check(const aarmvs_fusion_points_args* a) {
   if (!a) return fail(AARMVS_ERR_INVALID, "fusion_points: null args");
   if (a->H < 1 || a->W < 1 || (long long)a->H * a->W >= (1LL << 31))
     return fail(AARMVS_ERR_INVALID, "fusion_points: need H, W >= 1 and H * W < 2^31");
@@ -1246,8 +1248,55 @@ int aarmvs_fusion_points(const aarmvs_fusion_points_args* a, hipStream_t stream)
     return fail(AARMVS_ERR_INVALID, "fusion_points: null xyz with capacity > 0");
   if ((a->color == nullptr) != (a->rgb == nullptr))
     return fail(AARMVS_ERR_INVALID, "fusion_points: color and rgb must both be set or both be null");
-  hipError_t e = launch_fusion_points(a, stream);
+  return AARMVS_OK;
+}
+
+int aarmvs_fusion_points(const aarmvs_fusion_points_args* a, hipStream_t stream) {
+  if (int rc = fusion_points_check(a)) return rc;
+  hipError_t e = launch_fusion_points(a, nullptr, nullptr, stream);
   return e == hipSuccess ? AARMVS_OK : hip_fail(e, "fusion_points");
+}
+
+int aarmvs_fusion_points_normals(const aarmvs_fusion_points_args* a, const float* normal_map, float* nxyz,
+                                 hipStream_t stream) {
+  if (!normal_map && !nxyz) return aarmvs_fusion_points(a, stream);
+  if (int rc = fusion_points_check(a)) return rc;
+  if (!normal_map || !nxyz)
+    return fail(AARMVS_ERR_INVALID,
+                "fusion_points_normals: normal_map and nxyz must both be set or both be null");
+  hipError_t e = launch_fusion_points(a, normal_map, nxyz, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "fusion_points_normals");
+}
+
+// [p, p + n) and [q, q + m) share a byte
+static bool ranges_overlap(const void* p, size_t n, const void* q, size_t m) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + m && b < a + n;
+}
+
+int aarmvs_fusion_normals(const aarmvs_fusion_normals_args* a, hipStream_t stream) {
+  if (!a) return fail(AARMVS_ERR_INVALID, "fusion_normals: null args");
+  if (a->H < 1 || a->W < 1 || (long long)a->H * a->W >= (1LL << 31))
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: need H, W >= 1 and H * W < 2^31");
+  if (!a->depth || !a->valid || !a->cams || !a->normal)
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: null pointer argument");
+  if (a->radius < 1 || a->radius > AARMVS_MAX_NORMAL_RADIUS)
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: radius must be 1, 2 or 3");
+  const int window = (2 * a->radius + 1) * (2 * a->radius + 1);
+  if (a->min_count < 3 || a->min_count > window)
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: min_count must be in 3 .. (2 radius + 1)^2");
+  if (!(a->max_rel_jump >= 0.0f) || std::isinf(a->max_rel_jump))
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: max_rel_jump must be finite and >= 0");
+  // other blocks still read depth and valid while a block writes its outputs
+  const size_t px = (size_t)a->H * a->W;
+  if (ranges_overlap(a->normal, 12 * px, a->depth, 8 * px) || ranges_overlap(a->normal, 12 * px, a->valid, px))
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: normal must not alias depth or valid");
+  if (a->has_normal &&
+      (ranges_overlap(a->has_normal, px, a->depth, 8 * px) || ranges_overlap(a->has_normal, px, a->valid, px) ||
+       ranges_overlap(a->has_normal, px, a->normal, 12 * px)))
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: has_normal must not alias depth, valid or normal");
+  hipError_t e = launch_fusion_normals(a, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "fusion_normals");
 }
 
 size_t aarmvs_group_norm_scratch_bytes(int B, int C, int HW) {

@@ -297,6 +297,13 @@ struct PointsArgs {
   const int* block_off;
 };
 
+// the instantiation with normals (aarmvs_fusion_points_normals): the plain arguments, then the
+// view's normal map and the kept pixels' normals
+struct PointsNormalsArgs : PointsArgs {
+  const float* normal_map;
+  float* nxyz;
+};
+
 __global__ void __launch_bounds__(kPtsThreads) points_count_kernel(const unsigned char* __restrict__ mask,
                                                                    int HW, int* __restrict__ block_cnt) {
   __shared__ int wcnt[kPtsWaves];
@@ -348,7 +355,11 @@ __global__ void __launch_bounds__(kScanThreads) points_scan_kernel(int* __restri
   if (threadIdx.x == 0) *total = carry;
 }
 
-__global__ void __launch_bounds__(kPtsThreads) points_write_kernel(PointsArgs a) {
+// NORMALS = false is the plain write pass.  NORMALS = true also copies the kept pixel's normal to
+// its rank: nxyz lines up with xyz and rgb.
+template <bool NORMALS>
+__global__ void __launch_bounds__(kPtsThreads)
+points_write_kernel(std::conditional_t<NORMALS, PointsNormalsArgs, PointsArgs> a) {
   __shared__ int wcnt[kPtsRounds][kPtsWaves];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const long long base = (long long)blockIdx.x * kPtsChunk;
@@ -391,6 +402,13 @@ __global__ void __launch_bounds__(kPtsThreads) points_write_kernel(PointsArgs a)
       q[1] = (unsigned char)(int)__fmul_rn(c[1], 255.0f);
       q[2] = (unsigned char)(int)__fmul_rn(c[2], 255.0f);
     }
+    if constexpr (NORMALS) {
+      const float* nm = a.normal_map + (size_t)p * 3;
+      float* no = a.nxyz + (size_t)rank * 3;
+      no[0] = nm[0];
+      no[1] = nm[1];
+      no[2] = nm[2];
+    }
   }
 }
 
@@ -402,8 +420,10 @@ size_t fusion_points_workspace_bytes(int H, int W) {
   return ((size_t)points_blocks(H, W) * sizeof(int) + 255) / 256 * 256;
 }
 
-hipError_t launch_fusion_points(const aarmvs_fusion_points_args* in, hipStream_t s) {
-  PointsArgs a{};
+// normal_map == nullptr: the plain write pass (nxyz is not looked at)
+hipError_t launch_fusion_points(const aarmvs_fusion_points_args* in, const float* normal_map, float* nxyz,
+                                hipStream_t s) {
+  PointsNormalsArgs a{};
   a.HW = in->H * in->W;
   a.W = in->W;
   a.mask = in->mask;
@@ -420,7 +440,153 @@ hipError_t launch_fusion_points(const aarmvs_fusion_points_args* in, hipStream_t
   ProfScope ps(s, K_FUSION_POINTS);
   hipLaunchKernelGGL(points_count_kernel, dim3(nb), dim3(kPtsThreads), 0, s, a.mask, a.HW, blk);
   hipLaunchKernelGGL(points_scan_kernel, dim3(1), dim3(kScanThreads), 0, s, blk, nb, in->count);
-  hipLaunchKernelGGL(points_write_kernel, dim3(nb), dim3(kPtsThreads), 0, s, a);
+  if (normal_map != nullptr) {
+    a.normal_map = normal_map;
+    a.nxyz = nxyz;
+    hipLaunchKernelGGL(points_write_kernel<true>, dim3(nb), dim3(kPtsThreads), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(points_write_kernel<false>, dim3(nb), dim3(kPtsThreads), 0, s,
+                       static_cast<const PointsArgs&>(a));
+  }
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------
+// Per-pixel normals of a view's averaged depth map (aarmvs_fusion_normals, include/aarmvs.h): a
+// least-squares fit of 1/d = a x + b y + c over the usable pixels of a (2R+1)^2 window, in float64
+// with every operation rounded on its own and the sums in the header's order.  A block owns a
+// kNrmTY x kNrmTX tile: the depth of the tile and its R-wide halo goes to LDS once -- NaN where a
+// pixel is not usable or outside the image, which fails the per-tap gate by itself -- beside its
+// reciprocal, computed once per pixel.  A wave owns a tile row at a time, so its 8-byte LDS reads
+// are 64 consecutive doubles.  No atomics; the only global reads are the bounds-checked tile loads.
+// Algorithmic bytes per pixel: 9 read (+ halo) and 12 or 13 written.
+// ---------------------------------------------------------------------------------
+constexpr int kNrmTX = 64, kNrmTY = 16, kNrmThreads = 256;
+
+struct NormalsArgs {
+  int H, W, tiles_x, min_count;
+  const double* depth;
+  const unsigned char* valid;
+  float K[9], R[9];   // K, and the upper-left 3x3 of inv(E)
+  double max_rel_jump;
+  float* normal;
+  unsigned char* has_normal;
+};
+
+template <int R>
+__global__ void __launch_bounds__(kNrmThreads) fusion_normals_kernel(NormalsArgs a) {
+  constexpr int LH = kNrmTY + 2 * R, LW = kNrmTX + 2 * R;
+  __shared__ double sd[LH][LW];   // the depth of a usable pixel, else NaN
+  __shared__ double sw[LH][LW];   // 1 / sd
+  const int by = blockIdx.x / a.tiles_x, bx = blockIdx.x - by * a.tiles_x;
+  const int x_tile = bx * kNrmTX, y_tile = by * kNrmTY;
+  const double nan = __longlong_as_double(0x7ff8000000000000LL);
+  for (int j = threadIdx.x; j < LH * LW; j += kNrmThreads) {
+    const int ly = j / LW, lx = j - ly * LW;
+    const int gy = y_tile - R + ly, gx = x_tile - R + lx;
+    double d = nan;
+    if (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) {
+      const size_t q = (size_t)gy * a.W + gx;
+      const double t = a.depth[q];
+      if (a.valid[q] != 0 && t > 0.0 && t < __longlong_as_double(0x7ff0000000000000LL)) d = t;
+    }
+    sd[ly][lx] = d;
+    sw[ly][lx] = __ddiv_rn(1.0, d);
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int x0 = x_tile + tx;
+  if (x0 >= a.W) return;
+#pragma unroll 1
+  for (int k = 0; k < kNrmTY / 4; ++k) {
+    const int ty = wave + 4 * k, y0 = y_tile + ty;
+    if (y0 >= a.H) break;
+    const size_t p = (size_t)y0 * a.W + x0;
+    const double d0 = sd[ty + R][tx + R];
+    const double lim = __dmul_rn(a.max_rel_jump, d0);
+    int A = 0, B = 0, C = 0, D = 0, E = 0, N = 0;
+    double Suw = 0.0, Svw = 0.0, Sw = 0.0;
+#pragma unroll
+    for (int v = -R; v <= R; ++v) {
+#pragma unroll
+      for (int u = -R; u <= R; ++u) {
+        const double dq = sd[ty + R + v][tx + R + u];
+        // NaN (the centre's or the neighbour's) fails the comparison
+        if (fabs(__dsub_rn(dq, d0)) <= lim) {
+          const double w = sw[ty + R + v][tx + R + u];
+          A += u * u;
+          B += u * v;
+          C += v * v;
+          D += u;
+          E += v;
+          N += 1;
+          Suw = __dadd_rn(Suw, __dmul_rn((double)u, w));
+          Svw = __dadd_rn(Svw, __dmul_rn((double)v, w));
+          Sw = __dadd_rn(Sw, w);
+        }
+      }
+    }
+    // cofactors of the normal matrix: exact integers (below 2^31 for R <= 3)
+    const int c00 = C * N - E * E, c01 = D * E - B * N, c02 = B * E - C * D;
+    const int c11 = A * N - D * D, c12 = B * D - A * E, c22 = A * C - B * B;
+    const int det = (A * c00 + B * c01) + D * c02;
+    auto dot3 = [](double k0, double v0, double k1, double v1, double k2, double v2) {
+      return __dadd_rn(__dadd_rn(__dmul_rn(k0, v0), __dmul_rn(k1, v1)), __dmul_rn(k2, v2));
+    };
+    const double pa = dot3((double)c00, Suw, (double)c01, Svw, (double)c02, Sw);
+    const double pb = dot3((double)c01, Suw, (double)c11, Svw, (double)c12, Sw);
+    const double pc = dot3((double)c02, Suw, (double)c12, Svw, (double)c22, Sw);
+    const double cabs = __dsub_rn(__dsub_rn(pc, __dmul_rn(pa, (double)x0)), __dmul_rn(pb, (double)y0));
+    double m[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+      m[i] = dot3((double)a.K[i], pa, (double)a.K[3 + i], pb, (double)a.K[6 + i], cabs);
+    const double len = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(m[0], m[0]), __dmul_rn(m[1], m[1])),
+                                      __dmul_rn(m[2], m[2])));
+    // (a NaN centre gathers nothing: N = 0)
+    const bool has = N >= a.min_count && det > 0 && len > 0.0 &&
+                     len < __longlong_as_double(0x7ff0000000000000LL);
+    float out[3] = {0.0f, 0.0f, 0.0f};
+    if (has) {
+      const double n0 = -__ddiv_rn(m[0], len), n1 = -__ddiv_rn(m[1], len), n2 = -__ddiv_rn(m[2], len);
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        out[i] = (float)dot3((double)a.R[3 * i], n0, (double)a.R[3 * i + 1], n1, (double)a.R[3 * i + 2], n2);
+    }
+    float* o = a.normal + p * 3;
+    o[0] = out[0];
+    o[1] = out[1];
+    o[2] = out[2];
+    if (a.has_normal != nullptr) a.has_normal[p] = has ? 1 : 0;
+  }
+}
+
+// (timed under the points' profile id: the list of kernel names is fixed)
+hipError_t launch_fusion_normals(const aarmvs_fusion_normals_args* in, hipStream_t s) {
+  NormalsArgs a{};
+  a.H = in->H;
+  a.W = in->W;
+  a.tiles_x = (in->W + kNrmTX - 1) / kNrmTX;
+  a.min_count = in->min_count;
+  a.depth = in->depth;
+  a.valid = in->valid;
+  for (int i = 0; i < 9; ++i) a.K[i] = in->cams[i];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) a.R[3 * i + j] = in->cams[9 + 4 * i + j];
+  a.max_rel_jump = (double)in->max_rel_jump;
+  a.normal = in->normal;
+  a.has_normal = in->has_normal;
+  // H W < 2^31, so the tiles are fewer than 2^31 too
+  const long long tiles = (long long)a.tiles_x * ((in->H + kNrmTY - 1) / kNrmTY);
+  if (tiles >= (1LL << 31)) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)tiles), block(kNrmThreads);
+  ProfScope ps(s, K_FUSION_POINTS);
+  switch (in->radius) {
+    case 1: hipLaunchKernelGGL(fusion_normals_kernel<1>, grid, block, 0, s, a); break;
+    case 2: hipLaunchKernelGGL(fusion_normals_kernel<2>, grid, block, 0, s, a); break;
+    case 3: hipLaunchKernelGGL(fusion_normals_kernel<3>, grid, block, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 

@@ -595,6 +595,72 @@ size_t aarmvs_fusion_points_workspace_bytes(int H, int W);
 int aarmvs_fusion_points(const aarmvs_fusion_points_args* args, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Opt-in per-point normals of the fused cloud (not in the reference).  A view's normal map comes
+ * from its averaged depth map alone: per pixel, a least-squares plane fit over a (2r+1)^2 window.
+ * For a pinhole camera a 3-D plane is affine in INVERSE depth over pixel coordinates, so the fit
+ * is the linear one 1/d = a x + b y + c, and the plane's normal is proportional to K^T (a, b, c).
+ * (A cross product of neighbour differences fails on winner-take-all depth, which is quantised to
+ * the depth planes: neighbours mostly share a depth and the differences are staircases.)
+ *
+ * Definition.  All arithmetic is float64, every operation rounded on its own (no fused
+ * multiply-add), sums evaluated left to right exactly as written.
+ *   Centre.  p = (x0, y0) is USABLE when valid[p] != 0 and d0 = depth[p] is finite and > 0;
+ *     otherwise it has no normal.
+ *   Neighbours.  q = (x0 + u, y0 + v), |u|, |v| <= r, is usable when it is inside the image, valid
+ *     with a finite depth > 0, and |depth[q] - d0| <= (double)max_rel_jump * d0.  The centre counts.
+ *   Sums.  Over the usable pixels of the window in row-major order (v outer, u inner), with
+ *     w = 1.0 / depth[q]:  the integers A = sum u^2, B = sum u v, C = sum v^2, D = sum u,
+ *     E = sum v, N = sum 1 (exact), and the rounded Suw = sum (u w), Svw = sum (v w), Sw = sum w.
+ *   Cofactors of the normal matrix (exact integers):
+ *     c00 = C N - E E   c01 = D E - B N   c02 = B E - C D
+ *     c11 = A N - D D   c12 = B D - A E   c22 = A C - B B      det = (A c00 + B c01) + D c02
+ *     det > 0 is an exact test for "the usable pixels are not collinear".
+ *   Plane, scaled by det (> 0: the direction is unchanged and nothing is divided by det):
+ *     a = (c00 Suw + c01 Svw) + c02 Sw
+ *     b = (c01 Suw + c11 Svw) + c12 Sw
+ *     c = (c02 Suw + c12 Svw) + c22 Sw          cabs = (c - a x0) - b y0
+ *   Camera-space normal:  m_i = (K[0][i] a + K[1][i] b) + K[2][i] cabs,
+ *     len = sqrt((m0^2 + m1^2) + m2^2),  n_cam = -(m / len).  The plane is m . P = det > 0 and the
+ *     camera sits at the origin, so -m faces the camera: no orientation test is needed.
+ *   World normal:  n_i = (R[i][0] n0 + R[i][1] n1) + R[i][2] n2, R the upper-left 3x3 of inv(E),
+ *     cast to float32.
+ *   A pixel HAS A NORMAL when it is usable, N >= min_count, det > 0 and len is finite and > 0;
+ *     otherwise normal = (0, 0, 0) and has_normal = 0.
+ * The kernel reads depth and valid only (9 B per pixel and the halo) and writes 12 or 13 B per
+ * pixel; no atomics, so the result is the same on every run.  `cams` is HOST memory: K 3x3 of the
+ * DEPTH MAP's pixel grid (Tanks and Temples: the halved intrinsics), then inv(E) 4x4, float32
+ * row-major (aarmvs/fusion.py packs them).
+ * AARMVS_ERR_INVALID, before any launch: a NULL depth, valid, cams or normal; H or W < 1 or
+ * H W >= 2^31; radius outside 1..AARMVS_MAX_NORMAL_RADIUS; min_count outside 3..(2r+1)^2;
+ * max_rel_jump negative or not finite; normal or has_normal overlapping depth or valid (other
+ * blocks still read them).
+ *
+ * aarmvs_fusion_points_normals is aarmvs_fusion_points with one more output: nxyz[rank] =
+ * normal_map[p] for every kept pixel p, the rank being the one the call computes anyway, so nxyz
+ * lines up with xyz and rgb.  normal_map == NULL and nxyz == NULL: it IS aarmvs_fusion_points;
+ * exactly one of them NULL is AARMVS_ERR_INVALID, as is everything aarmvs_fusion_points rejects.
+ * Both are timed under the profiler's "fusion_points" id (the list of kernel names is fixed).
+ * Measured on synthetic data only; the effect on DTU and Tanks and Temples meshes is not measured
+ * (no datasets here).
+ * ------------------------------------------------------------------------- */
+#define AARMVS_MAX_NORMAL_RADIUS 3
+#define AARMVS_FUSION_NORMAL_CAM_FLOATS 25      /* K 3x3 then inv(E) 4x4, float32 row-major, HOST */
+typedef struct aarmvs_fusion_normals_args {
+  int H, W;
+  const double* depth;          /* [H,W] device: the averaged depth (aarmvs_fusion_filter's depth_avg) */
+  const unsigned char* valid;   /* [H,W] device: nonzero = the pixel may take part in a fit */
+  const float* cams;            /* HOST, K of the DEPTH MAP's grid (T&T: the halved one), inv(E) */
+  int radius;                   /* r in 1..AARMVS_MAX_NORMAL_RADIUS: window (2r+1)^2 */
+  int min_count;                /* 3..(2r+1)^2: usable pixels a fit needs */
+  float max_rel_jump;           /* finite, >= 0: depth-discontinuity gate, relative to the centre */
+  float* normal;                /* [H,W,3] device out: unit world normal, or (0,0,0) where there is none */
+  unsigned char* has_normal;    /* [H,W] device out (0/1), or NULL */
+} aarmvs_fusion_normals_args;
+int aarmvs_fusion_normals(const aarmvs_fusion_normals_args* args, hipStream_t stream);
+int aarmvs_fusion_points_normals(const aarmvs_fusion_points_args* args, const float* normal_map /*[H,W,3]*/,
+                                 float* nxyz /*[capacity,3] out*/, hipStream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Epilogue of the evidential head (evidential/models.py:385-459): from the three
  * classifier outputs head[i] = classif_i(...) [1][4][D][H][W] (channels: cost, log nu, log
  * alpha, log beta; at the head's full [maxdisp, H, W] resolution, where get_pred / get_logits'
