@@ -684,6 +684,147 @@ __attribute__((amdgpu_waves_per_eu((XV & 8) ? 6 : (XV & 4) ? 5 : 4))) cost_x_ker
   }
 }
 
+// cost_x with PP planes per thread: a block takes planes kp0 .. kp0 + PP - 1 of its tile (fewer
+// in a ragged last block).  Consecutive planes of a sweep are spaced below a source pixel for
+// most (pixel, view)s, so plane j's four taps are usually plane j - 1's.  Per view, the taps of
+// the block's first plane are loaded into one register set R, and each later plane reloads R, in
+// place and under a divergent branch, only in the lanes whose tap floor (xf, yf) moved (a NaN
+// position never compares equal, so it reloads).  After plane j's step R holds plane j's taps in
+// every lane: the taps' validity and indices follow from the floor alone, so a lane that keeps R
+// reads exactly what it would have loaded.  Every (pixel, view, plane) runs cost_x_kernel<2>'s
+// operations in its order: results are bit-identical for every PP (AARMVS_COST_X_PLANES).
+// The omega weights (view v of a pixel computed by lane v & 1 of its pair, as there) wait in LDS,
+// [plane][view][pixel], instead of PP x AARMVS_MAX_SRC registers; a pair's lanes share a wave.
+template <int XR, int PP>
+__global__ void __launch_bounds__(2 * XR * kTileW)
+__attribute__((amdgpu_waves_per_eu(PP >= 4 ? 2 : 3))) cost_x_planes_kernel(
+    PipeArgs a, const float* __restrict__ P, const float* __restrict__ Rel) {
+  static_assert(3 * AARMVS_MAX_SRC * PP <= 2 * XR * kTileW, "one statistic per thread");
+  __shared__ GnStat gs[PP][AARMVS_MAX_SRC][3];
+  __shared__ float wl[PP][AARMVS_MAX_SRC][XR * kTileW];
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const int H = a.H, W = a.W, HW = H * W, nsrc = a.nsrc;
+  // the plane blocks of a tile are consecutive blocks of one XCD: their taps share its L2
+  const int seq = xcd_tile(blockIdx.x, gridDim.x);
+  const int nkb = (a.npl + PP - 1) / PP;
+  const int tile = seq / nkb, kp0 = (seq - tile * nkb) * PP;
+  const int np = min(PP, a.npl - kp0);   // this block's planes
+  const int tiles_x = (W + kTileW - 1) / kTileW;
+  const int h = tid & 1, q = tid >> 1;
+  const int gy = (tile / tiles_x) * XR + q / kTileW, gx = (tile % tiles_x) * kTileW + q % kTileW;
+  if (tid < 3 * nsrc * np) {
+    const int j = tid / (3 * nsrc), r = tid - j * 3 * nsrc;
+    const int v = r / 3, k = r % 3;
+    gs[j][v][k] =
+        stat_read(a.st_prev + (kp0 + j) * a.st_kstride + st_index(b, v, k, nsrc), 4.0 * HW);
+  }
+  __syncthreads();
+  if (gy >= H || gx >= W) return;
+  const uint32_t fbytes = (uint32_t)((size_t)kC * HW * 4);   // one view's c8 image
+  const size_t p = (size_t)gy * W + gx;
+  float dep[PP];
+  {
+    OmegaP o;
+    load_omega(a, P, o);
+#pragma unroll
+    for (int j = 0; j < PP; ++j) {
+      if (j >= np) continue;
+      const int kp = kp0 + j;
+      dep[j] = a.dvals[b * a.D + a.d_prev + kp];
+      const float4* __restrict__ t1p = a.t1_prev + kp * a.t1_kstride;
+      float* const omega_out = kp == a.omega_k ? a.omega_out : nullptr;
+      for (int vp = 0; vp < nsrc; vp += 2) {
+        const int vm = min(vp + h, nsrc - 1);
+        // 32-bit element offsets (B * nsrc * HW < 2^31, checked on the host)
+        const uint32_t p32 = (uint32_t)p, hw = (uint32_t)HW;
+        const float w = omega_weight(
+            t1p[(uint32_t)(b * nsrc + vp) * hw + (uint32_t)(vm - vp) * hw + p32], gs[j][vm], o);
+        if (vp + h < nsrc) {
+          if (omega_out) omega_out[(uint32_t)(vp * a.B + b) * hw + (uint32_t)(h * a.B) * hw + p32] = w;
+          wl[j][vp + h][q] = w;
+        }
+      }
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  // this lane's half of the reference feature (16 channels), read once for all views and planes
+  const __amdgpu_buffer_rsrc_t rref = uniform_rsrc(a.ref + (size_t)b * kC * HW, fbytes);
+  float4 rf[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) rf[c] = ld_c8(rref, (uint32_t)p, 2 * c + h, HW);
+  float acc[PP][16];
+#pragma unroll
+  for (int j = 0; j < PP; ++j)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+  for (int v = 0; v < nsrc; ++v) {
+    const float* __restrict__ m = Rel + 12 * (v * a.B + b);
+    const __amdgpu_buffer_rsrc_t rsrc = uniform_rsrc(a.src[v] + (size_t)b * kC * HW, fbytes);
+    float4 R[16];   // tap k of chunk c at R[4 c + k], of the plane last stepped
+    const Box none{0, 0, 0, 0};
+    TapP tp[PP];
+    bool moved[PP];   // plane j's tap floor differs from plane j - 1's
+    float wp1[PP];
+    // plane 0's loads go out first; the later planes' positions are computed under them
+    {
+      const TapF tf = tap_f(m, dep[0], gx, gy, H, W);
+      tp[0] = tap_p(tf, true, H, W, false, none, fbytes / 32u);
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) R[4 * c + k] = ld_c8(rsrc, tp[0].pix[k], 2 * c + h, HW);
+      wp1[0] = __fadd_rn(wl[0][v][q], 1.0f);
+      float pxf = tf.xf, pyf = tf.yf;
+#pragma unroll
+      for (int j = 1; j < PP; ++j) {
+        if (j >= np) continue;
+        const TapF tj = tap_f(m, dep[j], gx, gy, H, W);
+        tp[j] = tap_p(tj, true, H, W, false, none, fbytes / 32u);
+        moved[j] = !(tj.xf == pxf && tj.yf == pyf);
+        pxf = tj.xf;
+        pyf = tj.yf;
+        wp1[j] = __fadd_rn(wl[j][v][q], 1.0f);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < PP; ++j) {
+      if (j >= np) continue;
+      const TapP& t = tp[j];
+      // all 16 loads are issued before the first is consumed
+      if (j > 0 && moved[j]) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+          for (int k = 0; k < 4; ++k) R[4 * c + k] = ld_c8(rsrc, t.pix[k], 2 * c + h, HW);
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const float4 g = bil4(R[4 * c], R[4 * c + 1], R[4 * c + 2], R[4 * c + 3], t);
+        // x accumulation in view order (drmvsnet.py:311-316)
+        const float4 sq = sqdiff4(g, rf[c]);
+        float* ac = &acc[j][4 * c];
+        ac[0] = __fadd_rn(ac[0], __fmul_rn(wp1[j], sq.x));
+        ac[1] = __fadd_rn(ac[1], __fmul_rn(wp1[j], sq.y));
+        ac[2] = __fadd_rn(ac[2], __fmul_rn(wp1[j], sq.z));
+        ac[3] = __fadd_rn(ac[3], __fmul_rn(wp1[j], sq.w));
+      }
+    }
+  }
+  // NHWC: this lane's channels 8c + 4h .. +3 of pixel p, one 16-B store per chunk and plane
+#pragma unroll
+  for (int j = 0; j < PP; ++j) {
+    if (j >= np) continue;
+    float* xo = a.x + (kp0 + j) * a.x_kstride + ((size_t)b * HW + p) * kC + 4 * h;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float r[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) r[i] = -1.0f * __fdiv_rn(acc[j][4 * c + i], (float)nsrc);
+      *reinterpret_cast<float4*>(xo + 8 * c) = make_float4(r[0], r[1], r[2], r[3]);
+    }
+  }
+}
+
 // omega_conv LDS images (source box, reference tile, sq tile): 32-B pixels (one chunk),
 // the two 16-B halves of pixel p swapped when bit 3 of p is set, so that 16 consecutive
 // pixels' reads of one half cover all banks.  Piece i of an image (pixel i >> 1, slot
@@ -1343,6 +1484,15 @@ static int omega_ipb(int items, int cu_count) {
   return ipb;
 }
 
+// cost_x planes per thread (cost_x_kernel's PP): AARMVS_COST_X_PLANES=1|2|4 forces it for A/B
+// runs and the tests (results are bit-identical for every value)
+constexpr int kCostXPlanes = 2;
+static int cost_x_planes() {
+  const char* s = std::getenv("AARMVS_COST_X_PLANES");
+  const int v = (s && *s) ? std::atoi(s) : kCostXPlanes;
+  return v >= 4 ? 4 : v >= 2 ? 2 : 1;
+}
+
 static PipeArgs pipe_args_c8(const CostArgs& ca, const SweepGeom& g, const Workspace& ws) {
   PipeArgs a = pipe_args(ca, g, ws);
   // the pipeline reads the c8 copies of the features in the workspace
@@ -1371,9 +1521,15 @@ hipError_t launch_cost_x_group(const CostArgs& ca, const SweepGeom& g, const Wor
   a.omega_out = omega_out;
   a.omega_k = omega_out ? omega_k : -1;
   const int ntiles = ((g.W + kTileW - 1) / kTileW) * ((g.H + kXRows - 1) / kXRows);
+  const int pp = cost_x_planes();
+  const dim3 grid(ntiles * ((n + pp - 1) / pp), g.B), block(2 * kXRows * kTileW);
   ProfScope ps(s, K_COST_X);
-  hipLaunchKernelGGL(cost_x_kernel<2>, dim3(ntiles * n, g.B), dim3(2 * kXRows * kTileW), 0, s, a,
-                     a.params, a.rel);
+  if (pp == 4)
+    hipLaunchKernelGGL((cost_x_planes_kernel<kXRows, 4>), grid, block, 0, s, a, a.params, a.rel);
+  else if (pp == 2)
+    hipLaunchKernelGGL((cost_x_planes_kernel<kXRows, 2>), grid, block, 0, s, a, a.params, a.rel);
+  else
+    hipLaunchKernelGGL(cost_x_kernel<2>, grid, block, 0, s, a, a.params, a.rel);
   return hipGetLastError();
 }
 

@@ -153,6 +153,21 @@ int main(int argc, char** argv) {
     CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
     CK(hipEventElapsedTime(&ms, e0, e1));
     printf("cost_x npl=%d      %8.3f ms/plane  %7.0f GB/s algorithmic\n", npl, ms / 10 / npl, bx * npl / (ms / 10) / 1e6);
+    // PP planes per thread (cost_x_planes_kernel): the planes are 1 mm apart here, the
+    // headline sweep's spacing
+    auto planes = [&](int pp, auto kern) {
+      const dim3 grid(tiles_x * ((H + kXRows - 1) / kXRows) * ((npl + pp - 1) / pp), B);
+      auto go = [&] { hipLaunchKernelGGL(kern, grid, dim3(2 * kXRows * kTileW), 0, 0, c, dpar, drel); };
+      for (int i = 0; i < 2; ++i) go();
+      CK(hipDeviceSynchronize());
+      CK(hipEventRecord(e0));
+      for (int i = 0; i < 10; ++i) go();
+      CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
+      CK(hipEventElapsedTime(&ms, e0, e1));
+      printf("cost_x npl=%d PP=%d %8.3f ms/plane\n", npl, pp, ms / 10 / npl);
+    };
+    if (npl >= 2) planes(2, cost_x_planes_kernel<kXRows, 2>);
+    if (npl >= 4) planes(4, cost_x_planes_kernel<kXRows, 4>);
     if (npl == 8) {
       auto c4 = [&] { hipLaunchKernelGGL((cost_x_kernel<2, 4>), dim3(tiles_x * ((H + 3) / 4) * npl, B), dim3(2 * 4 * kTileW), 0, 0, c, dpar, drel); };
       for (int i = 0; i < 2; ++i) c4();

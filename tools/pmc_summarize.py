@@ -14,7 +14,7 @@ import os
 import re
 from collections import defaultdict
 
-SHORT = [("cost_x_kernel", "cost_x"), ("omega_conv_kernel", "omega_conv"), ("omega_mfma_kernel", "omega_conv"),
+SHORT = [("cost_x_kernel", "cost_x"), ("cost_x_planes_kernel", "cost_x"), ("omega_conv_kernel", "omega_conv"), ("omega_mfma_kernel", "omega_conv"),
          ("omega_stats_kernel<1>", "omega_stats1"),
          ("omega_stats_kernel<2>", "omega_stats2"), ("deconv_mfma_kernel", "deconv"), ("deconv_px2_kernel", "deconv"), ("deconv_px_kernel", "deconv"), ("deconv_kernel", "deconv"), ("head_wta", "head_wta"), ("nchw_to_c8", "to_c8"), ("fusion_filter_kernel", "fusion"),
          ("cbw_feat_kernel", "cbw_feat"), ("dgrad_kernel<64>", "dgrad64"), ("dgrad_kernel<32>", "dgrad32"),
