@@ -290,7 +290,7 @@ struct PipeArgs {
   // the launch's grouping and of block timing)
   double* part;
   int part_n;
-  int omega_ipb;              // omega_mfma: items per block (AARMVS_OMEGA_IPB, default 1)
+  int omega_ipb;              // omega_mfma: planes per block (AARMVS_OMEGA_IPB, default 1)
 };
 
 template <typename PA>
@@ -958,7 +958,8 @@ struct OmegaPos {
 };
 // The block's GroupNorm partial of an item is summed over the block's waves one item later (by
 // thread 0, after the next item's first barrier; the kernel sums the last item's after its
-// loop): no barrier of its own.  wsum[par][wave] holds item parity par's wave sums.
+// loop): no barrier of its own.  wsum[par][q][wave] holds the wave sums of plane q of the item
+// of parity par.
 template <int NW>
 __device__ __forceinline__ void omega_block_sum(const double (*ws)[2], double& s0, double& s1) {
   s0 = 0.0;
@@ -969,26 +970,41 @@ __device__ __forceinline__ void omega_block_sum(const double (*ws)[2], double& s
   }
 }
 
-template <int ABL, int TW, bool BAL, typename PA>
-__device__ __forceinline__ void omega_item(PA& a, const float* __restrict__ P,
+// LDS of an item (declared by the kernel, shared by its one- and two-plane item bodies): chunk
+// c's source box and reference pixels, then (after the last chunk) the row-sum images zm, zp
+// (16 B per haloed pixel each, per plane)
+template <int TW>
+struct OmegaLds {
+  using T = OmegaTile<TW>;
+  static constexpr int kRefFl = (T::BOXPX + 1) * 8;
+  static constexpr int YFL = kRefFl + 2 * T::NT * 4;
+  static_assert(2 * 2 * T::NT * 4 <= YFL, "two planes' row-sum images fit in the box space");
+};
+
+// PP: planes per item (1, or 2: planes ip.kp and ip.kp + 1 of one (tile, view) on one source
+// box, the union of both planes' taps: one box reduce, one set of box and reference DMAs, B
+// fragments and chunk barriers per pair; each plane's own arithmetic is that of PP = 1, so the
+// results are bit-identical).  KPP: the kernel's largest PP (the previous item had nprev <= KPP
+// planes pv.kp, pv.kp + 1, their wave sums in wsum[par ^ 1]).  PP = 2 returns false, with the
+// previous item's block sums done and nothing else, when the union box does not fit the LDS
+// capacity: the caller runs the two planes as single items.
+template <int ABL, int TW, bool BAL, int PP, int KPP, typename PA>
+__device__ __forceinline__ bool omega_item(PA& a, const float* __restrict__ P,
                                            const float* __restrict__ Rel,
                                            const unsigned* __restrict__ xbound, const OmegaPos ip,
-                                           double (*wsum)[OmegaTile<TW>::NT / 64][2], int par,
-                                           bool has_prev, const OmegaPos pv) {
+                                           double (*wsum)[KPP][OmegaTile<TW>::NT / 64][2], int par,
+                                           int nprev, const OmegaPos pv, float* const smem,
+                                           int (*red)[4]) {
   using T = OmegaTile<TW>;
   constexpr int kMThreads = T::NT, kMBoxPx = T::BOXPX, kMOutH = T::OUTH, kMOutW = T::OUTW;
   constexpr int NB = (2 * kMBoxPx + kMThreads - 1) / kMThreads;   // box pieces per thread
   static_assert(TW == 16 || TW == 32, "the row sums shift by DPP along one haloed row");
-  // LDS: chunk c's source box and reference pixels, then (after the last chunk) the row-sum
-  // images zm, zp (16 B per haloed pixel each)
-  constexpr int kRefFl = (kMBoxPx + 1) * 8;
-  constexpr int YFL = kRefFl + 2 * kMThreads * 4;
-  static_assert(2 * kMThreads * 4 <= YFL, "the row-sum images fit in the box space");
-  __shared__ __attribute__((aligned(16))) float smem[YFL];
+  static_assert(PP == 1 || PP == 2, "one plane or a plane pair per item");
+  static_assert(PP <= KPP, "the wave sums hold KPP planes per item");
+  constexpr int kRefFl = OmegaLds<TW>::kRefFl;
   float* const box = smem;
   float4* const zms = reinterpret_cast<float4*>(smem);
   float4* const zps = zms + kMThreads;
-  __shared__ int red[kMThreads / 64][4];
   int tid;
   asm volatile("v_mov_b32 %0, %1" : "=v"(tid) : "v"((int)threadIdx.x));   // see omega_mfma_kernel
   const int lane = tid & 63, wave = tid >> 6;
@@ -1004,36 +1020,52 @@ __device__ __forceinline__ void omega_item(PA& a, const float* __restrict__ P,
   // rimg[(h NT + t) 4], after the box (conflict-free, lane-linear reads)
   float* const rimg = smem + kRefFl;
 
-  const float dep = a.dvals[b * a.D + a.d_next + kp];
   const float* __restrict__ m = Rel + 12 * (v * a.B + b);
   const uint32_t fbytes = (uint32_t)((size_t)kC * HW * 4);
   const uint32_t cbytes = (uint32_t)HW * 32u;
   const __amdgpu_buffer_rsrc_t rref = uniform_rsrc(a.ref + (size_t)b * kC * HW, fbytes);
   const __amdgpu_buffer_rsrc_t rsrc = uniform_rsrc(a.src[v] + (size_t)b * kC * HW, fbytes);
-  TapF tf{};
+  TapF tf[PP] = {};
   int lx = INT_MAX, ly = INT_MAX, bhx = INT_MIN, bhy = INT_MIN;
-  if (in_img) {
-    if constexpr ((ABL & 16) != 0) {
-      tf.xf = (float)gx + 0.25f * dep * 1e-3f;
-      tf.yf = (float)gy;
-      tf.wt[0] = tf.wt[1] = tf.wt[2] = tf.wt[3] = 0.25f;
-      tf.xf = floorf(tf.xf);
-    } else {
-      tf = tap_f(m, dep, gx, gy, H, W);
+#pragma unroll
+  for (int q = 0; q < PP; ++q) {
+    const float dep = a.dvals[b * a.D + a.d_next + kp + q];
+    if (in_img) {
+      if constexpr ((ABL & 16) != 0) {
+        tf[q].xf = (float)gx + 0.25f * dep * 1e-3f;
+        tf[q].yf = (float)gy;
+        tf[q].wt[0] = tf[q].wt[1] = tf[q].wt[2] = tf[q].wt[3] = 0.25f;
+        tf[q].xf = floorf(tf[q].xf);
+      } else {
+        tf[q] = tap_f(m, dep, gx, gy, H, W);
+      }
+      box_extend(tf[q], H, W, lx, ly, bhx, bhy);
     }
-    box_extend(tf, H, W, lx, ly, bhx, bhy);
   }
   const Box bx = box_reduce<kMThreads / 64>(lx, ly, bhx, bhy, red);
   // after box_reduce's barrier: every wave is past the previous item's row-sum reads and wave sums
-  if (tid < 8) box[kMBoxPx * 8 + tid] = 0.f;   // the zero pixel
-  if (has_prev && tid == 0) {
-    double s0, s1;
-    omega_block_sum<kMThreads / 64>(wsum[par ^ 1], s0, s1);
-    if (!(ABL & 64)) part_put(a, pv.kp, b, pv.v, pv.tile, s0, s1);
+  if constexpr (PP == 1) {
+    if (tid < 8) box[kMBoxPx * 8 + tid] = 0.f;   // the zero pixel
+  }
+  if (nprev && tid == 0) {
+#pragma unroll
+    for (int q = 0; q < KPP; ++q) {
+      if (q < nprev) {
+        double s0, s1;
+        omega_block_sum<kMThreads / 64>(wsum[par ^ 1][q], s0, s1);
+        if (!(ABL & 64)) part_put(a, pv.kp + q, b, pv.v, pv.tile, s0, s1);
+      }
+    }
   }
   const bool lds = bx.nx * bx.ny <= min(kMBoxPx, a.box_cap);
+  if constexpr (PP > 1) {
+    if (!lds) return false;   // (block-uniform: bx is)
+    if (tid < 8) box[kMBoxPx * 8 + tid] = 0.f;   // the zero pixel
+  }
   const uint32_t zp = lds ? (uint32_t)kMBoxPx : fbytes / 32u;
-  TapP tp = tap_p4(tf, in_img, H, W, lds, bx, zp);
+  TapP tp[PP];
+#pragma unroll
+  for (int q = 0; q < PP; ++q) tp[q] = tap_p4(tf[q], in_img, H, W, lds, bx, zp);
   const int items = lds ? bx.nx * bx.ny * 2 : 0;
   const uint32_t mg = box_magic(bx.nx);
   uint32_t boff[NB];
@@ -1076,15 +1108,19 @@ __device__ __forceinline__ void omega_item(PA& a, const float* __restrict__ P,
   }
   const float dsc = ldexpf(1.0f, -(e / 2));
 #pragma unroll
-  for (int k = 0; k < 4; ++k) tp.wt[k] = __fmul_rn(tp.wt[k], dsc);
+  for (int q = 0; q < PP; ++q)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) tp[q].wt[k] = __fmul_rn(tp[q].wt[k], dsc);
   const float* __restrict__ w0t = P + a.off_ow0t;   // [9][32][4]: centre tap = tap 4
   const half8* __restrict__ owm = reinterpret_cast<const half8*>(P + a.off_owm);
-  floatx16 acc0, acc1;   // first written by chunk 0's MFMAs (ABL 1: zero here)
+  floatx16 acc0[PP], acc1[PP];   // first written by chunk 0's MFMAs (ABL 1: zero here)
   if constexpr ((ABL & 1) != 0) {
 #pragma unroll
-    for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
+    for (int q = 0; q < PP; ++q)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc0[q][r] = acc1[q][r] = 0.f;
   }
-  float o4[4] = {0.f, 0.f, 0.f, 0.f};
+  float o4[PP][4] = {};
 
   stage(0);
   dma_wait();
@@ -1092,108 +1128,148 @@ __device__ __forceinline__ void omega_item(PA& a, const float* __restrict__ P,
 #pragma unroll 1
   for (int c = 0; c < 4; ++c) {
     const float* const bx_c = box;
-    // sample the own pixel (8 channels) and form sq
-    float4 g0, g1;
-    if (ABL & 4) {
-      g0 = g1 = make_float4(tp.wt[0], tp.wt[1], tp.wt[2], tp.wt[3]);
-    } else if (lds) {
-      g0 = bil4(img_ld(bx_c, tp.pix[0], 0), img_ld(bx_c, tp.pix[1], 0), img_ld(bx_c, tp.pix[2], 0),
-                img_ld(bx_c, tp.pix[3], 0), tp);
-      g1 = bil4(img_ld(bx_c, tp.pix[0], 1), img_ld(bx_c, tp.pix[1], 1), img_ld(bx_c, tp.pix[2], 1),
-                img_ld(bx_c, tp.pix[3], 1), tp);
-    } else {
-      g0 = bil4(ld_c8(rsrc, tp.pix[0], 2 * c, HW), ld_c8(rsrc, tp.pix[1], 2 * c, HW),
-                ld_c8(rsrc, tp.pix[2], 2 * c, HW), ld_c8(rsrc, tp.pix[3], 2 * c, HW), tp);
-      g1 = bil4(ld_c8(rsrc, tp.pix[0], 2 * c + 1, HW), ld_c8(rsrc, tp.pix[1], 2 * c + 1, HW),
-                ld_c8(rsrc, tp.pix[2], 2 * c + 1, HW), ld_c8(rsrc, tp.pix[3], 2 * c + 1, HW), tp);
-    }
     // the reference pixel from LDS (DMA'd with the box: a register prefetch carried across
     // the chunk loop cost 16 register copies per chunk)
-    const float4 rf0 = *reinterpret_cast<const float4*>(rimg + tid * 4);
-    const float4 rf1 = *reinterpret_cast<const float4*>(rimg + (kMThreads + tid) * 4);
+    // (a pair reads it once, ahead of both planes' sampling; one plane after its box reads)
+    float4 rf0, rf1;
+    auto ref_read = [&]() {
+      rf0 = *reinterpret_cast<const float4*>(rimg + tid * 4);
+      rf1 = *reinterpret_cast<const float4*>(rimg + (kMThreads + tid) * 4);
+    };
+    if constexpr (PP > 1) ref_read();
     // sq 2^-e: (2^(-e/2) g - 2^(-e/2) r)^2, the difference rounded once as in sqdiff4
     auto dsq = [&](float g, float r) {
       const float dd = __fmaf_rn(r, -dsc, g);
       return __fmul_rn(dd, dd);
     };
-    const float sq[8] = {dsq(g0.x, rf0.x), dsq(g0.y, rf0.y), dsq(g0.z, rf0.z), dsq(g0.w, rf0.w),
-                         dsq(g1.x, rf1.x), dsq(g1.y, rf1.y), dsq(g1.z, rf1.z), dsq(g1.w, rf1.w)};
+    // sample the own pixel (8 channels) of plane q and form sq
+    auto sample = [&](int q, float (&sq)[8]) {
+      const TapP& t = tp[q];
+      float4 g0, g1;
+      if (ABL & 4) {
+        g0 = g1 = make_float4(t.wt[0], t.wt[1], t.wt[2], t.wt[3]);
+      } else if (PP > 1 || lds) {
+        g0 = bil4(img_ld(bx_c, t.pix[0], 0), img_ld(bx_c, t.pix[1], 0), img_ld(bx_c, t.pix[2], 0),
+                  img_ld(bx_c, t.pix[3], 0), t);
+        g1 = bil4(img_ld(bx_c, t.pix[0], 1), img_ld(bx_c, t.pix[1], 1), img_ld(bx_c, t.pix[2], 1),
+                  img_ld(bx_c, t.pix[3], 1), t);
+      } else {
+        g0 = bil4(ld_c8(rsrc, t.pix[0], 2 * c, HW), ld_c8(rsrc, t.pix[1], 2 * c, HW),
+                  ld_c8(rsrc, t.pix[2], 2 * c, HW), ld_c8(rsrc, t.pix[3], 2 * c, HW), t);
+        g1 = bil4(ld_c8(rsrc, t.pix[0], 2 * c + 1, HW), ld_c8(rsrc, t.pix[1], 2 * c + 1, HW),
+                  ld_c8(rsrc, t.pix[2], 2 * c + 1, HW), ld_c8(rsrc, t.pix[3], 2 * c + 1, HW), t);
+      }
+      if constexpr (PP == 1) ref_read();
+      sq[0] = dsq(g0.x, rf0.x);
+      sq[1] = dsq(g0.y, rf0.y);
+      sq[2] = dsq(g0.z, rf0.z);
+      sq[3] = dsq(g0.w, rf0.w);
+      sq[4] = dsq(g1.x, rf1.x);
+      sq[5] = dsq(g1.y, rf1.y);
+      sq[6] = dsq(g1.z, rf1.z);
+      sq[7] = dsq(g1.w, rf1.w);
+    };
+    half8 Bd, Bl, Bl2;
+    // plane q's centre tap, fp16 split and MFMAs on its sq
+    auto accumulate = [&](int q, const float (&sq)[8]) {
+      // centre tap (omega.reweight_network.0.0, tap 4) on the own pixel, fp32 (BAL)
+      {
+        const float* wt = w0t + (4 * kC + 8 * c) * 4;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+#pragma unroll
+          for (int co = 0; co < 4; ++co) o4[q][co] = fmaf(sq[j], wt[j * 4 + co], o4[q][co]);
+      }
+      // split sq 2^-e into fp16 hi + lo.  Out-of-image pixels (the conv's zero padding) already
+      // have sq = 0: zero bilinear weights on the box's zero pixel (or past the buffer) and a
+      // reference read past the buffer.  Two values per v_cvt_pk_f16_f32.
+      uint32_t hw[4], lw[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) hw[i] = split_pair(sq[2 * i], sq[2 * i + 1], lw[i]);
+      // after the swaps, (hw, lw) are the pixel operands of the wave's pixels 0-31 (lanes 0-31
+      // hi, 32-63 lo of pixel lane & 31) and of its pixels 32-63
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const auto r = __builtin_amdgcn_permlane32_swap(hw[i], lw[i], false, false);
+        hw[i] = r[0];
+        lw[i] = r[1];
+      }
+      // BAL: odd chunks accumulate the negated sum (accumulators and A negated), so the matrix
+      // cores' downward rounding alternates sign
+      if (BAL && (c & 1)) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          hw[i] ^= 0x80008000u;
+          lw[i] ^= 0x80008000u;
+        }
+      }
+      if (BAL && c > 0) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          acc0[q][r] = -acc0[q][r];
+          acc1[q][r] = -acc1[q][r];
+        }
+      }
+      const half8 A0 = __builtin_bit_cast(half8, u32x4{hw[0], hw[1], hw[2], hw[3]});
+      const half8 A1 = __builtin_bit_cast(half8, u32x4{lw[0], lw[1], lw[2], lw[3]});
+      if constexpr ((ABL & 128) != 0) {
+        Bd = A1;
+        Bl = A0;
+        Bl2 = A1;
+      }
+      // D^T = W x [sq hi | sq lo]^T: the weight fragments as the A operand, so that a lane holds
+      // its pixel's tap slots (rows) rather than a slot's pixels: row r of lane l is slot
+      // 2 (r >> 2) + (l >> 5), output channel r & 3 (the row sums below)
+      if (!(ABL & 1)) {
+        if (c == 0) {   // the accumulators start from the MFMA's inline-zero C operand (no zero fill)
+          const floatx16 z = {};
+          acc0[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bd, A0, z, 0, 0, 0);
+          acc1[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bd, A1, z, 0, 0, 0);
+        } else {
+          acc0[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bd, A0, acc0[q], 0, 0, 0);
+          acc1[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bd, A1, acc1[q], 0, 0, 0);
+        }
+        acc0[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bl, A0, acc0[q], 0, 0, 0);
+        acc1[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bl, A1, acc1[q], 0, 0, 0);
+        acc0[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bl2, A0, acc0[q], 0, 0, 0);
+        acc1[q] = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bl2, A1, acc1[q], 0, 0, 0);
+      } else {
+        acc0[q][0] += (float)A0[0] + (float)Bd[1];
+        acc1[q][0] += (float)A1[0] + (float)Bl[1];
+      }
+    };
     // this chunk's B fragments, issued before the barrier: their L1/L2 latency is hidden
     // behind it and the centre-tap chain (2.5% of the kernel against loading them after;
     // DMA'ing all 12 to LDS once per item instead was 1.8%)
-    half8 Bd, Bl, Bl2;
-    if constexpr ((ABL & 128) == 0) {
-      Bd = owm[(c * 3 + 0) * 64 + lane];
-      Bl = owm[(c * 3 + 1) * 64 + lane];
-      Bl2 = owm[(c * 3 + 2) * 64 + lane];
+    auto fragments = [&]() {
+      if constexpr ((ABL & 128) == 0) {
+        Bd = owm[(c * 3 + 0) * 64 + lane];
+        Bl = owm[(c * 3 + 1) * 64 + lane];
+        Bl2 = owm[(c * 3 + 2) * 64 + lane];
+      }
+    };
+    // Every plane samples first: the barrier then frees the box for chunk c + 1's DMA, which
+    // runs under all the planes' arithmetic.  (A pair that accumulated its first plane before
+    // sampling the second held the reference pixel and the fragments across that sampling:
+    // 168 VGPRs with 11 spilled; this order holds 8 sq values instead.)
+    float sq[PP][8];
+#pragma unroll
+    for (int q = 0; q < PP; ++q) {
+      // (one plane's eight box reads at a time: all sixteen in flight spilled 52 VGPRs)
+      sample(q, sq[q]);
+      // a pair's sq are formed here, plane by plane: left to itself the compiler keeps both
+      // planes' sixteen box reads in flight and sinks the bilinear chains below the barrier
+      // (64 VGPRs of taps across it: 52 spilled)
+      if constexpr (PP > 1) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(sq[q][j]));
+      }
     }
+    fragments();
     __syncthreads();   // every lane's box and reference reads of chunk c are done
     if (c < 3) stage(c + 1);
-    // centre tap (omega.reweight_network.0.0, tap 4) on the own pixel, fp32 (BAL)
-    {
-      const float* wt = w0t + (4 * kC + 8 * c) * 4;
 #pragma unroll
-      for (int j = 0; j < 8; ++j)
-#pragma unroll
-        for (int co = 0; co < 4; ++co) o4[co] = fmaf(sq[j], wt[j * 4 + co], o4[co]);
-    }
-    // split sq 2^-e into fp16 hi + lo.  Out-of-image pixels (the conv's zero padding) already
-    // have sq = 0: zero bilinear weights on the box's zero pixel (or past the buffer) and a
-    // reference read past the buffer.  Two values per v_cvt_pk_f16_f32.
-    uint32_t hw[4], lw[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) hw[i] = split_pair(sq[2 * i], sq[2 * i + 1], lw[i]);
-    // after the swaps, (hw, lw) are the pixel operands of the wave's pixels 0-31 (lanes 0-31 hi,
-    // 32-63 lo of pixel lane & 31) and of its pixels 32-63
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const auto r = __builtin_amdgcn_permlane32_swap(hw[i], lw[i], false, false);
-      hw[i] = r[0];
-      lw[i] = r[1];
-    }
-    // BAL: odd chunks accumulate the negated sum (accumulators and A negated), so the matrix
-    // cores' downward rounding alternates sign
-    if (BAL && (c & 1)) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        hw[i] ^= 0x80008000u;
-        lw[i] ^= 0x80008000u;
-      }
-    }
-    if (BAL && c > 0) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        acc0[r] = -acc0[r];
-        acc1[r] = -acc1[r];
-      }
-    }
-    const half8 A0 = __builtin_bit_cast(half8, u32x4{hw[0], hw[1], hw[2], hw[3]});
-    const half8 A1 = __builtin_bit_cast(half8, u32x4{lw[0], lw[1], lw[2], lw[3]});
-    if constexpr ((ABL & 128) != 0) {
-      Bd = A1;
-      Bl = A0;
-      Bl2 = A1;
-    }
-    // D^T = W x [sq hi | sq lo]^T: the weight fragments as the A operand, so that a lane holds
-    // its pixel's tap slots (rows) rather than a slot's pixels: row r of lane l is slot
-    // 2 (r >> 2) + (l >> 5), output channel r & 3 (the row sums below)
-    if (!(ABL & 1)) {
-      if (c == 0) {   // the accumulators start from the MFMA's inline-zero C operand (no zero fill)
-        const floatx16 z = {};
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bd, A0, z, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bd, A1, z, 0, 0, 0);
-      } else {
-        acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bd, A0, acc0, 0, 0, 0);
-        acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bd, A1, acc1, 0, 0, 0);
-      }
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bl, A0, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bl, A1, acc1, 0, 0, 0);
-      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bl2, A0, acc0, 0, 0, 0);
-      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(Bl2, A1, acc1, 0, 0, 0);
-    } else {
-      acc0[0] += (float)A0[0] + (float)Bd[1];
-      acc1[0] += (float)A1[0] + (float)Bl[1];
-    }
+    for (int q = 0; q < PP; ++q) accumulate(q, sq[q]);
     if (c < 3) {
       dma_wait();
       __syncthreads();   // chunk c+1's box and reference visible
@@ -1218,62 +1294,70 @@ __device__ __forceinline__ void omega_item(PA& a, const float* __restrict__ P,
   auto shl1 = [](float x) {
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), kShl, 0xF, 0xF, true));
   };
-  float zmr[4], zpr[4], z0[4];
+  // (plane q's images at zms / zps + 2 q NT)
+  float zmr[PP][4], zpr[PP][4], z0[PP][4];
 #pragma unroll
-  for (int co = 0; co < 4; ++co) {
-    const float r0 = (shr1(acc0[co]) + acc0[4 + co]) + shl1(acc0[8 + co]);
-    const float r1 = (shr1(acc1[co]) + acc1[4 + co]) + shl1(acc1[8 + co]);
-    // -> Z_-1 of the wave's pixel `lane` in zmr, Z_+1 in zpr
-    const auto zz = __builtin_amdgcn_permlane32_swap(__float_as_uint(r0), __float_as_uint(r1), false, false);
-    zmr[co] = __uint_as_float(zz[0]);
-    zpr[co] = __uint_as_float(zz[1]);
-    // -> tap 3 and tap 5 of pixel `lane`
-    const auto t35 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc0[12 + co]),
-                                                      __float_as_uint(acc1[12 + co]), false, false);
-    z0[co] = shr1(__uint_as_float(t35[0])) + shl1(__uint_as_float(t35[1]));
-  }
-  // the row-sum images over the box space: every lane passed chunk 3's box reads before the
-  // barrier in the loop
-  if constexpr ((ABL & 32) == 0) {
-    zms[tid] = make_float4(zmr[0], zmr[1], zmr[2], zmr[3]);
-    zps[tid] = make_float4(zpr[0], zpr[1], zpr[2], zpr[3]);
+  for (int q = 0; q < PP; ++q) {
+#pragma unroll
+    for (int co = 0; co < 4; ++co) {
+      const float r0 = (shr1(acc0[q][co]) + acc0[q][4 + co]) + shl1(acc0[q][8 + co]);
+      const float r1 = (shr1(acc1[q][co]) + acc1[q][4 + co]) + shl1(acc1[q][8 + co]);
+      // -> Z_-1 of the wave's pixel `lane` in zmr, Z_+1 in zpr
+      const auto zz = __builtin_amdgcn_permlane32_swap(__float_as_uint(r0), __float_as_uint(r1), false, false);
+      zmr[q][co] = __uint_as_float(zz[0]);
+      zpr[q][co] = __uint_as_float(zz[1]);
+      // -> tap 3 and tap 5 of pixel `lane`
+      const auto t35 = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc0[q][12 + co]),
+                                                        __float_as_uint(acc1[q][12 + co]), false, false);
+      z0[q][co] = shr1(__uint_as_float(t35[0])) + shl1(__uint_as_float(t35[1]));
+    }
+    // the row-sum images over the box space: every lane passed chunk 3's box reads before the
+    // barrier in the loop
+    if constexpr ((ABL & 32) == 0) {
+      zms[2 * q * kMThreads + tid] = make_float4(zmr[q][0], zmr[q][1], zmr[q][2], zmr[q][3]);
+      zps[2 * q * kMThreads + tid] = make_float4(zpr[q][0], zpr[q][1], zpr[q][2], zpr[q][3]);
+    }
   }
   __syncthreads();
-  // GroupNorm partials in fp64 from the first addition on (var = E[x^2] - E[x]^2 cancels)
-  double ps = 0.0, pss = 0.0;
-  if (interior) {
-    float g4[4];
-    if constexpr ((ABL & 32) != 0) {
 #pragma unroll
-      for (int co = 0; co < 4; ++co) g4[co] = (zmr[co] + z0[co]) + zpr[co];
-    } else {
-      const float4 up = zms[tid - TW], dn = zps[tid + TW];
-      g4[0] = (up.x + z0[0]) + dn.x;
-      g4[1] = (up.y + z0[1]) + dn.y;
-      g4[2] = (up.z + z0[2]) + dn.z;
-      g4[3] = (up.w + z0[3]) + dn.w;
-    }
-    if (BAL) {   // chunk 3 left -sum in the accumulators
+  for (int q = 0; q < PP; ++q) {
+    // GroupNorm partials in fp64 from the first addition on (var = E[x^2] - E[x]^2 cancels)
+    double ps = 0.0, pss = 0.0;
+    if (interior) {
+      float g4[4];
+      if constexpr ((ABL & 32) != 0) {
 #pragma unroll
-      for (int co = 0; co < 4; ++co) g4[co] = -g4[co];
+        for (int co = 0; co < 4; ++co) g4[co] = (zmr[q][co] + z0[q][co]) + zpr[q][co];
+      } else {
+        const float4 up = zms[2 * q * kMThreads + tid - TW], dn = zps[2 * q * kMThreads + tid + TW];
+        g4[0] = (up.x + z0[q][0]) + dn.x;
+        g4[1] = (up.y + z0[q][1]) + dn.y;
+        g4[2] = (up.z + z0[q][2]) + dn.z;
+        g4[3] = (up.w + z0[q][3]) + dn.w;
+      }
+      if (BAL) {   // chunk 3 left -sum in the accumulators
+#pragma unroll
+        for (int co = 0; co < 4; ++co) g4[co] = -g4[co];
+      }
+      const float pe = ldexpf(1.0f, e);
+      const float isc = P[a.off_owm_scale] * pe;
+      const float* __restrict__ b0 = P + a.off_ob0;
+      float4 out;
+      out.x = fmaf(g4[0], isc, o4[q][0] * pe) + b0[0];
+      out.y = fmaf(g4[1], isc, o4[q][1] * pe) + b0[1];
+      out.z = fmaf(g4[2], isc, o4[q][2] * pe) + b0[2];
+      out.w = fmaf(g4[3], isc, o4[q][3] * pe) + b0[3];
+      a.t1_next[(kp + q) * a.t1_kstride + ((size_t)b * nsrc + v) * HW + gy * W + gx] = out;
+      ps = ((double)out.x + (double)out.y) + ((double)out.z + (double)out.w);
+      pss = ((double)out.x * out.x + (double)out.y * out.y) + ((double)out.z * out.z + (double)out.w * out.w);
     }
-    const float pe = ldexpf(1.0f, e);
-    const float isc = P[a.off_owm_scale] * pe;
-    const float* __restrict__ b0 = P + a.off_ob0;
-    float4 out;
-    out.x = fmaf(g4[0], isc, o4[0] * pe) + b0[0];
-    out.y = fmaf(g4[1], isc, o4[1] * pe) + b0[1];
-    out.z = fmaf(g4[2], isc, o4[2] * pe) + b0[2];
-    out.w = fmaf(g4[3], isc, o4[3] * pe) + b0[3];
-    a.t1_next[kp * a.t1_kstride + ((size_t)b * nsrc + v) * HW + gy * W + gx] = out;
-    ps = ((double)out.x + (double)out.y) + ((double)out.z + (double)out.w);
-    pss = ((double)out.x * out.x + (double)out.y * out.y) + ((double)out.z * out.z + (double)out.w * out.w);
+    wave_sum2_d(ps, pss);
+    if (lane == 0) {
+      wsum[par][q][wave][0] = ps;
+      wsum[par][q][wave][1] = pss;
+    }
   }
-  wave_sum2_d(ps, pss);
-  if (lane == 0) {
-    wsum[par][wave][0] = ps;
-    wsum[par][wave][1] = pss;
-  }
+  return true;
 }
 
 // The kernel: a block takes a.omega_ipb consecutive items (omega_ipb()).  A tile's (view, plane)
@@ -1283,11 +1367,21 @@ __device__ __forceinline__ void omega_item(PA& a, const float* __restrict__ P,
 #ifndef AARMVS_OMEGA_WAVES
 #define AARMVS_OMEGA_WAVES 4
 #endif
-template <int ABL = 0, int TW = kOmegaTW, bool BAL = false>
-__global__ void __launch_bounds__(OmegaTile<TW>::NT) __attribute__((amdgpu_waves_per_eu(AARMVS_OMEGA_WAVES)))
+// KPP = 2: items seq, seq + 1 of a block that are planes kp, kp + 1 of one (tile, view) run as
+// one plane-pair item (omega_item's PP = 2); a last odd item, or a pair whose union box does not
+// fit the LDS capacity, runs as today's single items.  The pair's second accumulators cost a
+// wave per SIMD (3).  Grid, tile order and the meaning of omega_ipb (planes per block) do not
+// depend on KPP.  KPP = 1 keeps the one-plane kernel's item loop as it was.
+template <int ABL = 0, int TW = kOmegaTW, bool BAL = false, int KPP = 1>
+__global__ void __launch_bounds__(OmegaTile<TW>::NT)
+__attribute__((amdgpu_waves_per_eu(KPP > 1 ? 3 : AARMVS_OMEGA_WAVES)))
 omega_mfma_kernel(PipeArgs a, const float* __restrict__ P, const float* __restrict__ Rel,
                   const unsigned* __restrict__ xbound) {
   if (blockDim.x != OmegaTile<TW>::NT) return;   // LDS images are sized for exactly this block
+  __shared__ __attribute__((aligned(16))) float smem[OmegaLds<TW>::YFL];
+  // box_reduce's scratch: the pair attempt has its own, since a pair that does not fit is
+  // followed by a single item's reduce with no barrier between
+  __shared__ int red[KPP][OmegaTile<TW>::NT / 64][4];
   const int ipb = a.omega_ipb > 1 ? a.omega_ipb : 1;
   const int npl = a.npl, nsrc = a.nsrc;
   const int tiles_x = (a.W + OmegaTile<TW>::OUTW - 1) / OmegaTile<TW>::OUTW;
@@ -1304,17 +1398,79 @@ omega_mfma_kernel(PipeArgs a, const float* __restrict__ P, const float* __restri
     ip.tx = ip.tile - ip.ty * tiles_x;
   }
   constexpr int NW = OmegaTile<TW>::NT / 64;
-  __shared__ double wsum[2][NW][2];
+  __shared__ double wsum[2][KPP][NW][2];
   OmegaPos pv = ip;
-  int it = 0;
+  if constexpr (KPP == 1) {
+    int it = 0;
 #pragma unroll 1
-  for (; it < ipb; ++it) {
-    if (seq0 + it >= total) break;
-    // (no barrier between items: the next item's LDS writes all follow box_reduce's barrier,
-    // which every wave reaches after the previous item's last LDS read)
-    if (it) {
+    for (; it < ipb; ++it) {
+      if (seq0 + it >= total) break;
+      // (no barrier between items: the next item's LDS writes all follow box_reduce's barrier,
+      // which every wave reaches after the previous item's last LDS read)
+      if (it) {
+        pv = ip;
+        if (++ip.kp == npl) {
+          ip.kp = 0;
+          if (++ip.v == nsrc) {
+            ip.v = 0;
+            ++ip.tile;
+            if (++ip.tx == tiles_x) {
+              ip.tx = 0;
+              ++ip.ty;
+            }
+          }
+        }
+      }
+      // the item reads the arguments through a pointer the compiler cannot prove invariant
+      // across items: otherwise it hoists every argument load out of the loop (SGPR spills)
+      uint32_t z;
+      asm volatile("s_mov_b32 %0, 0" : "=s"(z));
+      typedef const __attribute__((address_space(4))) PipeArgs KPipeArgs;
+      KPipeArgs& ka = *(KPipeArgs*)((const __attribute__((address_space(4))) char*)&a + z);
+      omega_item<ABL, TW, BAL, 1, 1>(ka, P, Rel, xbound, ip, wsum, it & 1, it > 0, pv, smem, red[0]);
+    }
+    if (it > 0) {   // the last item's block sum
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        double s0, s1;
+        omega_block_sum<NW>(wsum[(it - 1) & 1][0], s0, s1);
+        if (!(ABL & 64)) part_put(a, ip.kp, (int)blockIdx.z, ip.v, ip.tile, s0, s1);
+      }
+    }
+  } else {
+    // it: planes done; np: planes of the item that ran last (0: none, or its block sums are done);
+    // par: parity of the items run; singles: planes left of a pair that runs as single items
+    int it = 0, np = 0, par = 0, singles = 0;
+#pragma unroll 1
+    while (it < ipb && seq0 + it < total) {
+      // (no barrier between items: the next item's LDS writes all follow box_reduce's barrier,
+      // which every wave reaches after the previous item's last LDS read)
+      // the item reads the arguments through a pointer the compiler cannot prove invariant
+      // across items: otherwise it hoists every argument load out of the loop (SGPR spills)
+      uint32_t z;
+      asm volatile("s_mov_b32 %0, 0" : "=s"(z));
+      typedef const __attribute__((address_space(4))) PipeArgs KPipeArgs;
+      KPipeArgs& ka = *(KPipeArgs*)((const __attribute__((address_space(4))) char*)&a + z);
+      int done = 0;
+      if (singles == 0 && it + 1 < ipb && seq0 + it + 1 < total && ip.kp + 1 < npl) {
+        if (omega_item<ABL, TW, BAL, 2, KPP>(ka, P, Rel, xbound, ip, wsum, par, np, pv, smem, red[1]))
+          done = 2;
+        else {
+          np = 0;
+          singles = 2;
+        }
+      }
+      if (done == 0) {
+        omega_item<ABL, TW, BAL, 1, KPP>(ka, P, Rel, xbound, ip, wsum, par, np, pv, smem, red[0]);
+        done = 1;
+        if (singles) --singles;
+      }
       pv = ip;
-      if (++ip.kp == npl) {
+      np = done;
+      par ^= 1;
+      it += done;
+      ip.kp += done;
+      if (ip.kp == npl) {   // (a pair never crosses a view's last plane)
         ip.kp = 0;
         if (++ip.v == nsrc) {
           ip.v = 0;
@@ -1326,20 +1482,18 @@ omega_mfma_kernel(PipeArgs a, const float* __restrict__ P, const float* __restri
         }
       }
     }
-    // the item reads the arguments through a pointer the compiler cannot prove invariant
-    // across items: otherwise it hoists every argument load out of the loop (SGPR spills)
-    uint32_t z;
-    asm volatile("s_mov_b32 %0, 0" : "=s"(z));
-    typedef const __attribute__((address_space(4))) PipeArgs KPipeArgs;
-    KPipeArgs& ka = *(KPipeArgs*)((const __attribute__((address_space(4))) char*)&a + z);
-    omega_item<ABL, TW, BAL>(ka, P, Rel, xbound, ip, wsum, it & 1, it > 0, pv);
-  }
-  if (it > 0) {   // the last item's block sum
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      double s0, s1;
-      omega_block_sum<NW>(wsum[(it - 1) & 1], s0, s1);
-      if (!(ABL & 64)) part_put(a, ip.kp, (int)blockIdx.z, ip.v, ip.tile, s0, s1);
+    if (np > 0) {   // the last item's block sums
+      __syncthreads();
+      if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < KPP; ++q) {
+          if (q < np) {
+            double s0, s1;
+            omega_block_sum<NW>(wsum[par ^ 1][q], s0, s1);
+            if (!(ABL & 64)) part_put(a, pv.kp + q, (int)blockIdx.z, pv.v, pv.tile, s0, s1);
+          }
+        }
+      }
     }
   }
 }
@@ -1484,6 +1638,17 @@ static int omega_ipb(int items, int cu_count) {
   return ipb;
 }
 
+// omega_mfma planes per item of the inference sweep (omega_mfma_kernel's KPP):
+// AARMVS_OMEGA_PLANES=1|2, read per launch, for A/B runs and the tests (results are
+// bit-identical for both values).  Default 2: the measurements are in DESIGN.md section 4 and
+// profiles/omega_planes_ab.txt.
+constexpr int kOmegaPlanes = 2;
+static int omega_planes() {
+  const char* s = std::getenv("AARMVS_OMEGA_PLANES");
+  const int v = (s && *s) ? std::atoi(s) : kOmegaPlanes;
+  return v >= 2 ? 2 : 1;
+}
+
 // cost_x planes per thread (cost_x_kernel's PP): AARMVS_COST_X_PLANES=1|2|4 forces it for A/B
 // runs and the tests (results are bit-identical for every value)
 constexpr int kCostXPlanes = 2;
@@ -1553,8 +1718,11 @@ hipError_t launch_omega_group(const CostArgs& ca, const SweepGeom& g, const Work
     a.part_n = ntiles;
     a.omega_ipb = omega_ipb(ntiles * g.nsrc * n * g.B, g.cu_count);
     const int nblk = (ntiles * g.nsrc * n + a.omega_ipb - 1) / a.omega_ipb;
-    if (balanced)
+    if (balanced)   // (the training sweep stays at one plane per item)
       hipLaunchKernelGGL((omega_mfma_kernel<0, kOmegaTW, true>), dim3(nblk, 1, g.B),
+                         dim3(OmegaTile<kOmegaTW>::NT), 0, s, a, a.params, a.rel, ws.xbound);
+    else if (n > 1 && a.omega_ipb > 1 && omega_planes() == 2)
+      hipLaunchKernelGGL((omega_mfma_kernel<0, kOmegaTW, false, 2>), dim3(nblk, 1, g.B),
                          dim3(OmegaTile<kOmegaTW>::NT), 0, s, a, a.params, a.rel, ws.xbound);
     else
       hipLaunchKernelGGL((omega_mfma_kernel<0, kOmegaTW>), dim3(nblk, 1, g.B),

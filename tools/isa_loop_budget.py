@@ -37,6 +37,10 @@ def main():
             m = re.search(r"Depth=(\d+)", ln)
             depth = int(m.group(1)) if m else 0
             continue
+        # a long block name pushes the loop annotation to a comment line of its own
+        m = re.match(r";\s+in Loop: .*Depth=(\d+)", s)
+        if m:
+            depth = int(m.group(1))
         if not s or s.startswith((";", ".")):
             continue
         c = classify(s.split()[0])

@@ -132,6 +132,40 @@ int main(int argc, char** argv) {
       ablate("skeleton - Y/atomics/B (255)", omega_mfma_kernel<255, 16>, t1b, stb);
       ablate("no Y image (32)", omega_mfma_kernel<32, 16>, t1b, stb);
       ablate("no B loads (128)", omega_mfma_kernel<128, 16>, t1b, stb);
+      // 8 items per block (the library's headline default), one plane per item against plane
+      // pairs (omega_mfma_kernel's KPP = 2), and the pair form's ablations
+      auto ablate8 = [&](const char* name, auto kern) {
+        PipeArgs a8 = a;
+        a8.omega_ipb = 8;
+        const dim3 grid8((ntm * nsrc * 8 + 7) / 8, 1, B);
+        for (int i = 0; i < 2; ++i) hipLaunchKernelGGL(kern, grid8, dim3(OmegaTile<16>::NT), 0, 0, a8, dpar, drel, ws.xbound);
+        CK(hipDeviceSynchronize());
+        CK(hipEventRecord(e0));
+        for (int i = 0; i < 5; ++i) hipLaunchKernelGGL(kern, grid8, dim3(OmegaTile<16>::NT), 0, 0, a8, dpar, drel, ws.xbound);
+        CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
+        float ms8; CK(hipEventElapsedTime(&ms8, e0, e1));
+        printf("omega_mfma npl=8 ipb=8 %-40s %8.3f ms/plane\n", name, ms8 / 5 / 8);
+      };
+      ablate8("one plane per item, default (0)", omega_mfma_kernel<0, 16, false, 1>);
+      ablate8("plane pairs, default (0)", omega_mfma_kernel<0, 16, false, 2>);
+      {
+        std::vector<float4> hp(2 * t1k), h1(2 * t1k);   // the first pair's planes
+        CK(hipMemcpy(hp.data(), t1b, 2 * t1k * 16, hipMemcpyDeviceToHost));
+        ablate8("one plane per item, again", omega_mfma_kernel<0, 16, false, 1>);
+        CK(hipMemcpy(h1.data(), t1b, 2 * t1k * 16, hipMemcpyDeviceToHost));
+        printf("  plane pairs vs one plane per item, t1 of planes 0 and 1: %s\n",
+               memcmp(hp.data(), h1.data(), 2 * t1k * 16) ? "DIFFERENT" : "identical");
+      }
+      ablate8("one plane: no MFMA (1)", omega_mfma_kernel<1, 16, false, 1>);
+      ablate8("pairs:     no MFMA (1)", omega_mfma_kernel<1, 16, false, 2>);
+      ablate8("one plane: no box DMA (2)", omega_mfma_kernel<2, 16, false, 1>);
+      ablate8("pairs:     no box DMA (2)", omega_mfma_kernel<2, 16, false, 2>);
+      ablate8("one plane: no sampling (4)", omega_mfma_kernel<4, 16, false, 1>);
+      ablate8("pairs:     no sampling (4)", omega_mfma_kernel<4, 16, false, 2>);
+      ablate8("one plane: no DMA/sampling/MFMA/ref (15)", omega_mfma_kernel<15, 16, false, 1>);
+      ablate8("pairs:     no DMA/sampling/MFMA/ref (15)", omega_mfma_kernel<15, 16, false, 2>);
+      ablate8("one plane: skeleton (31)", omega_mfma_kernel<31, 16, false, 1>);
+      ablate8("pairs:     skeleton (31)", omega_mfma_kernel<31, 16, false, 2>);
     }
     // plane npl-1 must equal a single-plane launch at d_next = npl
     if (npl > 1) {
