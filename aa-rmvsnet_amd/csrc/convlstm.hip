@@ -15,6 +15,7 @@
 // the deconv outputs) is NHWC, [B][H][W][C] fp32.
 #include <hip/hip_runtime.h>
 
+#include <cfloat>
 #include <cstdlib>
 #include <cstring>
 
@@ -1695,6 +1696,11 @@ __global__ void __launch_bounds__(256) posterior_from_cost_kernel(
 // rescaled running sum in one (online softmax, one exp per element: e = exp(-|v - m|)
 // serves both the rescale of the sum when v raises the max and the new term otherwise),
 // then exp(v - m) / sum.  Four planes' loads in flight per iteration.
+// Non-finite columns come out as torch.softmax's three passes give them: the running max starts
+// at -FLT_MAX, not -inf, so a -inf cost is a term of exactly 0 (v - m = -inf, not -inf + inf =
+// NaN) and a column of nothing but -inf is 0 * (1 / 0) = NaN; an infinite final max adds m - m =
+// NaN to the sum, which is what the three-pass form's own exp(m - m) term does.  For a finite
+// column m - m = 0 and every bit is as before.
 __global__ void __launch_bounds__(256) softmax_depth_kernel(const float* __restrict__ cost,
                                                             float* __restrict__ prob, int D,
                                                             int HW) {
@@ -1702,7 +1708,7 @@ __global__ void __launch_bounds__(256) softmax_depth_kernel(const float* __restr
   for (int p = blockIdx.x * blockDim.x + threadIdx.x; p < HW; p += gridDim.x * blockDim.x) {
     const float* c = cost + (size_t)b * D * HW + p;
     float* o = prob + (size_t)b * D * HW + p;
-    float m = -INFINITY, s = 0.f;
+    float m = -FLT_MAX, s = 0.f;
     auto add = [&](float v) {
       const float dv = v - m;
       const float e = expf(-fabsf(dv));
@@ -1722,7 +1728,7 @@ __global__ void __launch_bounds__(256) softmax_depth_kernel(const float* __restr
       for (int u = 0; u < 4; ++u) add(v[u]);
     }
     for (; d < D; ++d) add(c[(size_t)d * HW]);
-    const float inv = 1.0f / s;
+    const float inv = 1.0f / (s + (m - m));
     for (d = 0; d + 4 <= D; d += 4) {
       float v[4];
 #pragma unroll

@@ -66,7 +66,8 @@ __device__ __forceinline__ void moe_nig_bwd(const NigEst& a, const NigEst& b, co
   gb.la = gq * (d2 * d2);
   const float gu = g.u - gd1 - gd2;   // u also enters through d1, d2
   const float gn = gu / la;
-  const float gla = g.la - gu * n / (la * la);
+  // gu n / la^2 as (gu / la) (n / la): la^2 underflows for evidence below ~1e-19 (logits under -44)
+  const float gla = g.la - gn * u;
   ga.la += gla + gn * a.u;
   gb.la += gla + gn * b.u;
   ga.u += gn * a.la;

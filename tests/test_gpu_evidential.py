@@ -18,10 +18,11 @@ import os
 import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import GOLDEN
 from aarmvs import synthetic as syn
+
+from epilogue_cases import epilogue64 as _epilogue64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -69,27 +70,6 @@ def test_head_on_gpu_matches_reference():
         assert ops.profile_read()["evidential"][0] == 2
     finally:
         ops.profile_enable(False)
-
-
-def _epilogue64(heads, dv):
-    """float64 restatement of evidential/models.py:421-459 on [1,4,D,H,W] classifier outputs."""
-    ests, probs = [], []
-    sp = lambda x: F.softplus(x)   # noqa: E731
-    for o in heads:
-        cost, la, al, be = (o[:, i] for i in range(4))
-        p = F.softmax(cost, dim=1)
-        pred = (p * dv.view(1, -1, 1, 1)).sum(1)
-        ests.append((pred, sp((la * p).sum(1)), sp((al * p).sum(1)) + 1, sp((be * p).sum(1))))
-        probs.append(p)
-
-    def moe(a, b):
-        u1, la1, al1, be1 = a
-        u2, la2, al2, be2 = b
-        la = la1 + la2
-        u = (la1 * u1 + u2 * la2) / la
-        return u, la, al1 + al2 + 0.5, be1 + be2 + 0.5 * (la1 * (u1 - u) ** 2 + la2 * (u2 - u) ** 2)
-    r = moe(moe(ests[0], ests[1]), ests[2])
-    return torch.cat(r), torch.stack(probs).mean(0)
 
 
 def _random_heads(H, W, seed):
