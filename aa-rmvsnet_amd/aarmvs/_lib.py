@@ -151,6 +151,28 @@ class FusionNormalsArgs(ctypes.Structure):
     ]
 
 
+CLOUD_MAX_RINGS = 32
+CLOUD_AXIS_BITS = 21
+MAX_THRESHOLDS = 8
+c_longlong, c_double = ctypes.c_longlong, ctypes.c_double
+
+
+class CloudNnArgs(ctypes.Structure):
+    """Mirror of ``aarmvs_cloud_nn_args``."""
+    _fields_ = [
+        ("query", c_void_p),
+        ("target", c_void_p),
+        ("target_keys", c_void_p),
+        ("target_ids", c_void_p),
+        ("nq", c_longlong), ("m", c_longlong),
+        ("origin", c_double * 3),
+        ("cell", c_double),
+        ("max_dist", ctypes.c_float),
+        ("dist_out", c_void_p),
+        ("index_out", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "aarmvs_last_error": (c_char_p, []),
@@ -210,6 +232,14 @@ SIGNATURES = {
     "aarmvs_fusion_points": (c_int, [ctypes.POINTER(FusionPointsArgs), c_void_p]),
     "aarmvs_fusion_normals": (c_int, [ctypes.POINTER(FusionNormalsArgs), c_void_p]),
     "aarmvs_fusion_points_normals": (c_int, [ctypes.POINTER(FusionPointsArgs), c_void_p, c_void_p, c_void_p]),
+    "aarmvs_cloud_keys": (c_int, [c_void_p, c_longlong, ctypes.POINTER(c_double), c_double, c_void_p, c_void_p]),
+    "aarmvs_cloud_nn": (c_int, [ctypes.POINTER(CloudNnArgs), c_void_p]),
+    "aarmvs_cloud_stats_scratch_bytes": (c_size_t, [c_longlong]),
+    "aarmvs_cloud_stats": (c_int, [c_void_p, c_longlong, ctypes.POINTER(ctypes.c_float), c_int, c_void_p,
+                                   c_void_p, c_void_p]),
+    "aarmvs_cloud_voxel_workspace_bytes": (c_size_t, [c_longlong]),
+    "aarmvs_cloud_voxel_centroids": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p,
+                                             c_void_p, c_void_p]),
     "aarmvs_evidential_epilogue": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p,
                                            c_void_p, c_void_p]),
     "aarmvs_evidential_epilogue_backward": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int,

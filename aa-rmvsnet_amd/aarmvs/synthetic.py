@@ -212,3 +212,35 @@ def fusion_views(H: int, W: int, nsrc: int, seed: int = 0):
         depths.append(d)
     conf = rng.random((H, W)).astype(np.float32)
     return depths, cams, conf
+
+
+def fusion_ground_truth(H: int, W: int, nsrc: int) -> np.ndarray:
+    """World points float32 [(nsrc + 1) H W, 3] of ``fusion_views``' scene: the noise-free, hole-free
+    ray cast of every view (view after view, pixels in row-major order), by ``fusion_views``'
+    formulas with no random draw -- the ground-truth cloud of the synthetic scan.  The cameras are
+    ``fusion_views``' (they do not depend on the seed)."""
+    f = np.float32(1.2 * W)
+    K = np.array([[f, 0, W / 2], [0, f, H / 2], [0, 0, 1]], np.float32)
+    ys, xs = np.mgrid[0:H, 0:W].astype(np.float64)
+    pts = []
+    for v in range(nsrc + 1):
+        th = 0.03 * (v - nsrc / 2)
+        R = np.array([[np.cos(th), 0, np.sin(th)], [0, 1, 0], [-np.sin(th), 0, np.cos(th)]])
+        t = np.array([-30.0 * (v - nsrc / 2), 2.0 * v, 0.0])
+        E = np.eye(4)
+        E[:3, :3] = R
+        E[:3, 3] = t
+        E_ = E.astype(np.float32)
+        Ki = np.linalg.inv(K.astype(np.float64))
+        rays = Ki @ np.stack([xs.ravel(), ys.ravel(), np.ones(H * W)])
+        R = E_[:3, :3].astype(np.float64)
+        t = E_[:3, 3].astype(np.float64)
+        o = -R.T @ t
+        dvec = R.T @ rays
+        lam = (600.0 + 0.05 * o[0] - o[2]) / (dvec[2] - 0.05 * dvec[0])
+        pw = o[:, None] + dvec * lam
+        bump = 4.0 * np.sin(pw[0] / 37.0) * np.cos(pw[1] / 23.0)
+        depth = lam * (1.0 + bump / 600.0)
+        # the pixel's camera-space point is rays * depth (rays have z = 1), i.e. o + dvec * depth
+        pts.append((o[:, None] + dvec * depth).T.astype(np.float32))
+    return np.ascontiguousarray(np.concatenate(pts, axis=0))

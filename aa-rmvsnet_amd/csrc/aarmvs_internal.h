@@ -166,6 +166,19 @@ hipError_t launch_fusion_points(const aarmvs_fusion_points_args* a, const float*
                                 hipStream_t s);
 // per-pixel normals of a view's averaged depth map (fusion.hip)
 hipError_t launch_fusion_normals(const aarmvs_fusion_normals_args* a, hipStream_t s);
+// point-cloud evaluation (cloud.hip): grid keys, the truncated nearest neighbour in a key-sorted
+// target, the distances' statistics (thresholds: a host array of nthr values) and the voxel
+// centroids of a key-sorted cloud; n == 0 / nq == 0 launch nothing (the statistics write zeros)
+hipError_t launch_cloud_keys(const float* xyz, long long n, const double* origin, double cell,
+                             long long* keys, hipStream_t s);
+hipError_t launch_cloud_nn(const aarmvs_cloud_nn_args* a, hipStream_t s);
+size_t cloud_stats_scratch_bytes(long long n);
+hipError_t launch_cloud_stats(const float* dist, long long n, const float* thresholds, int nthr, double* out,
+                              void* scratch, hipStream_t s);
+size_t cloud_voxel_workspace_bytes(long long n);
+hipError_t launch_cloud_voxel_centroids(const float* xyz, const long long* keys, long long n, float* out,
+                                        long long capacity, long long* count, void* workspace,
+                                        hipStream_t s);
 // xmax (optional, to_nhwc only): atomic max of |in| as float bits
 hipError_t launch_layout(const float* in, float* out, int B, int C, int HW, bool to_nhwc,
                          hipStream_t s, unsigned* xmax = nullptr);

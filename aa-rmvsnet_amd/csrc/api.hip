@@ -1478,4 +1478,96 @@ int aarmvs_depth_metrics(const float* depth_est, const float* depth_gt, const fl
   return e == hipSuccess ? AARMVS_OK : hip_fail(e, "depth_metrics");
 }
 
+// ---- point-cloud evaluation (cloud.hip) ----
+static bool cloud_count_ok(long long n) { return n >= 0 && n < (1LL << 31); }
+static bool cloud_cell_ok(double cell) { return std::isfinite(cell) && cell > 0.0; }
+
+int aarmvs_cloud_keys(const float* xyz, long long n, const double* origin, double cell, long long* keys_out,
+                      hipStream_t stream) {
+  if (!cloud_count_ok(n)) return fail(AARMVS_ERR_INVALID, "cloud_keys: need 0 <= n < 2^31");
+  if (!origin || (n > 0 && (!xyz || !keys_out)))
+    return fail(AARMVS_ERR_INVALID, "cloud_keys: null pointer argument");
+  if (!std::isfinite(origin[0]) || !std::isfinite(origin[1]) || !std::isfinite(origin[2]))
+    return fail(AARMVS_ERR_INVALID, "cloud_keys: origin must be finite");
+  if (!cloud_cell_ok(cell)) return fail(AARMVS_ERR_INVALID, "cloud_keys: cell must be finite and > 0");
+  if (n > 0 && ranges_overlap(keys_out, 8 * (size_t)n, xyz, 12 * (size_t)n))
+    return fail(AARMVS_ERR_INVALID, "cloud_keys: keys_out must not alias xyz");
+  hipError_t e = launch_cloud_keys(xyz, n, origin, cell, keys_out, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "cloud_keys");
+}
+
+int aarmvs_cloud_nn(const aarmvs_cloud_nn_args* a, hipStream_t stream) {
+  if (!a) return fail(AARMVS_ERR_INVALID, "cloud_nn: null args");
+  if (!cloud_count_ok(a->nq) || !cloud_count_ok(a->m))
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: need 0 <= nq, m < 2^31");
+  if ((a->nq > 0 && (!a->query || !a->dist_out)) || (a->m > 0 && (!a->target || !a->target_keys)))
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: null pointer argument");
+  if (!std::isfinite(a->origin[0]) || !std::isfinite(a->origin[1]) || !std::isfinite(a->origin[2]))
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: origin must be finite");
+  if (!cloud_cell_ok(a->cell)) return fail(AARMVS_ERR_INVALID, "cloud_nn: cell must be finite and > 0");
+  if (!(a->max_dist >= 0.0f) || std::isinf(a->max_dist))
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: max_dist must be finite and >= 0");
+  if ((double)a->max_dist / a->cell > (double)AARMVS_CLOUD_MAX_RINGS)
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: max_dist / cell exceeds AARMVS_CLOUD_MAX_RINGS");
+  // other threads still read the inputs while a thread writes its outputs
+  const size_t nq = (size_t)a->nq, m = (size_t)a->m;
+  const void* outs[2] = {a->dist_out, a->index_out};
+  for (int o = 0; o < 2; ++o) {
+    if (!outs[o] || nq == 0) continue;
+    if (ranges_overlap(outs[o], 4 * nq, a->query, 12 * nq) ||
+        (m > 0 && (ranges_overlap(outs[o], 4 * nq, a->target, 12 * m) ||
+                   ranges_overlap(outs[o], 4 * nq, a->target_keys, 8 * m) ||
+                   (a->target_ids && ranges_overlap(outs[o], 4 * nq, a->target_ids, 4 * m)))))
+      return fail(AARMVS_ERR_INVALID, o == 0 ? "cloud_nn: dist_out must not alias an input"
+                                             : "cloud_nn: index_out must not alias an input");
+  }
+  if (nq > 0 && a->index_out && ranges_overlap(a->dist_out, 4 * nq, a->index_out, 4 * nq))
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: dist_out and index_out must not alias");
+  hipError_t e = launch_cloud_nn(a, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "cloud_nn");
+}
+
+size_t aarmvs_cloud_stats_scratch_bytes(long long n) {
+  return cloud_count_ok(n) ? cloud_stats_scratch_bytes(n) : 0;
+}
+
+int aarmvs_cloud_stats(const float* dist, long long n, const float* thresholds, int n_thresholds, double* out,
+                       void* scratch, hipStream_t stream) {
+  if (!cloud_count_ok(n)) return fail(AARMVS_ERR_INVALID, "cloud_stats: need 0 <= n < 2^31");
+  if (n_thresholds < 0 || n_thresholds > AARMVS_MAX_THRESHOLDS)
+    return fail(AARMVS_ERR_INVALID, "cloud_stats: at most 8 thresholds");
+  if (!out || !scratch || (n > 0 && !dist) || (n_thresholds > 0 && !thresholds))
+    return fail(AARMVS_ERR_INVALID, "cloud_stats: null pointer argument");
+  // blocks still read dist while others write their partials, and the reduce writes out after
+  const size_t out_bytes = (3 + (size_t)n_thresholds) * sizeof(double), scr = cloud_stats_scratch_bytes(n);
+  if (n > 0 && (ranges_overlap(out, out_bytes, dist, 4 * (size_t)n) || ranges_overlap(scratch, scr, dist, 4 * (size_t)n)))
+    return fail(AARMVS_ERR_INVALID, "cloud_stats: out and scratch must not alias dist");
+  if (ranges_overlap(out, out_bytes, scratch, scr))
+    return fail(AARMVS_ERR_INVALID, "cloud_stats: out must not alias scratch");
+  hipError_t e = launch_cloud_stats(dist, n, thresholds, n_thresholds, out, scratch, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "cloud_stats");
+}
+
+size_t aarmvs_cloud_voxel_workspace_bytes(long long n) {
+  return cloud_count_ok(n) ? cloud_voxel_workspace_bytes(n) : 0;
+}
+
+int aarmvs_cloud_voxel_centroids(const float* sorted_xyz, const long long* sorted_keys, long long n,
+                                 float* out_xyz, long long capacity, long long* count, void* workspace,
+                                 hipStream_t stream) {
+  if (!cloud_count_ok(n)) return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: need 0 <= n < 2^31");
+  if (capacity < 0) return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: negative capacity");
+  if (!count || !workspace || (n > 0 && (!sorted_xyz || !sorted_keys)))
+    return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: null pointer argument");
+  if (capacity > 0 && !out_xyz)
+    return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: null out_xyz with capacity > 0");
+  if (n > 0 && capacity > 0 &&
+      (ranges_overlap(out_xyz, 12 * (size_t)capacity, sorted_xyz, 12 * (size_t)n) ||
+       ranges_overlap(out_xyz, 12 * (size_t)capacity, sorted_keys, 8 * (size_t)n)))
+    return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: out_xyz must not alias an input");
+  hipError_t e = launch_cloud_voxel_centroids(sorted_xyz, sorted_keys, n, out_xyz, capacity, count, workspace,
+                                              stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "cloud_voxel_centroids");
+}
+
 }  // extern "C"

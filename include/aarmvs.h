@@ -661,6 +661,97 @@ int aarmvs_fusion_points_normals(const aarmvs_fusion_points_args* args, const fl
                                  float* nxyz /*[capacity,3] out*/, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * Point-cloud evaluation (not in the reference): the one operation under the DTU accuracy /
+ * completeness figures and the Tanks and Temples precision / recall / F-score -- for every point
+ * of cloud A the distance to its nearest point of cloud B -- and what goes with it.  The official
+ * protocols (DTU's observation masks, ground-plane cut and reducePts; Tanks and Temples' alignment
+ * and cropping) need dataset files and are NOT implemented; aarmvs/cloud_eval.py computes the plain
+ * figures.
+ *
+ * Definition.  A cloud is float32 [n,3] device memory.  A GRID is (origin[3] float64, cell float64
+ * > 0).  All arithmetic is float64, every operation rounded on its own (no fused multiply-add).
+ *   Cell of a point.  i_a = floor(((double)p_a - origin_a) / cell) for a = x, y, z.  A point is IN
+ *     THE GRID when its three coordinates are finite and 0 <= i_a < 2^21; its KEY is the int64
+ *     (i_z << 42) | (i_y << 21) | i_x, and every other point's key is INT64_MAX.  x sits in the low
+ *     bits on purpose: in a key-sorted cloud the cells (i_x - r .. i_x + r, i_y, i_z) are one
+ *     contiguous span, so a ring of the search costs one binary search per (i_y, i_z) row.
+ *   Truncated nearest neighbour.  For query q, over all in-grid targets t_j:
+ *     d2_j = (dx dx + dy dy) + dz dz with dx = (double)q_x - (double)t_x, ... (exact differences);
+ *     the neighbour is the j with the smallest (d2_j, id_j) in lexicographic order, id_j =
+ *     target_ids[j] if that array is given, else j;  dist = (float)sqrt(d2), index = id.
+ *     d2 > (double)max_dist (double)max_dist, or no in-grid target:  dist = +inf, index = -1.
+ *     q has a non-finite coordinate:                                  dist = NaN,  index = -1.
+ *     q finite but outside the grid:                                  dist = +inf, index = -1.
+ *   The result is EXACT: it equals the brute-force minimum over all targets whenever that minimum
+ *   is <= max_dist.  How the search guarantees it:
+ *     Box.  Per axis, lo_a = cell(q_a - reach) and hi_a = cell(q_a + reach), clamped to the grid,
+ *       with reach = max_dist (1 + 2^-40).  The cell function is monotone in the coordinate, so
+ *       every target within max_dist has lo_a <= i_a <= hi_a on every axis; cells outside the box
+ *       are never looked at.  The box reaches at most ceil(max_dist / cell) + 1 cells from q's.
+ *     Rings.  k = 0, 1, ... up to the box's reach: the box's cells at Chebyshev distance k from q's
+ *       cell, row by row (a shell row: its whole x-span; an inner row: the two end cells).
+ *     Stopping rule.  After ring k >= 1 the search stops when best_d2 <= (k cell (1 - 2^-20))^2.
+ *       A target not looked at yet is k + 1 or more cells away along some axis; the rounding of the
+ *       two quotients can misplace a point by less than 2^-30 cells and d2 carries a relative
+ *       error below 2^-51, so its d2 is strictly above that bound: the RELATIVE SLACK 2^-20 on
+ *       k cell is the safety margin, and no tie is lost.  Never after ring 0 (the bound is 0, and an
+ *       equal target with a lower id may sit in the next cell).
+ * aarmvs_cloud_keys: keys_out[i] = the key of xyz[i].  Sorting is the caller's job (the Python
+ *   layer: a stable torch.sort and a gather).
+ * aarmvs_cloud_nn: `target` [m,3] sorted by key, `target_keys` [m] ascending with the INT64_MAX
+ *   entries last, `target_ids` int32 [m] or NULL, `index_out` int32 [nq] or NULL.  One thread per
+ *   query; sort the queries by the same key (and un-permute the results) so that neighbouring threads
+ *   walk the same spans.  AARMVS_ERR_INVALID, before any launch: a NULL required pointer; nq or m
+ *   < 0 or >= 2^31; origin not finite; cell not finite or <= 0; max_dist negative or not finite;
+ *   max_dist / cell > AARMVS_CLOUD_MAX_RINGS; an output overlapping an input or the other output.
+ *   nq == 0: a successful no-op.  m == 0: +inf / -1 (NaN / -1 for non-finite queries).
+ * aarmvs_cloud_stats: out[0] = the number of finite values of dist [n], out[1] = their fp64 sum,
+ *   out[2] = the number of NaN, out[3 + k] = the number of finite values < thresholds[k] (NaN and
+ *   inf never count); `thresholds` is a HOST array of n_thresholds <= AARMVS_MAX_THRESHOLDS values
+ *   (NULL if 0), `out` [3 + n_thresholds] doubles on the device, `scratch`
+ *   aarmvs_cloud_stats_scratch_bytes(n) bytes of device memory.  Sum order, fixed: a block owns
+ *   4096 consecutive values, thread t adds values t, t + 256, ... of the block in that order, the
+ *   256 threads are added by an xor butterfly per wave and then wave by wave, and one block adds the
+ *   blocks' partials the same way.  n == 0 writes zeros.  AARMVS_ERR_INVALID: n < 0 or >= 2^31, more
+ *   than AARMVS_MAX_THRESHOLDS thresholds, a NULL required pointer, `out` or `scratch` overlapping
+ *   `dist`, `out` overlapping `scratch`.
+ * aarmvs_cloud_voxel_centroids: one point per occupied cell of a KEY-SORTED cloud, in key order:
+ *   the float64 sum of the cell's points in sorted order (a stable sort makes that the original
+ *   order within a cell), divided by their number, cast to float32.  Points with key INT64_MAX are
+ *   dropped.  The output position of a cell is its rank (block counts of cell starts, an exclusive
+ *   scan, in-block ranks, as aarmvs_fusion_points).  Cells of rank >= capacity are not written;
+ *   `count` (device) always receives the number of occupied cells.  `workspace`:
+ *   aarmvs_cloud_voxel_workspace_bytes(n) bytes of device memory.  One thread adds a whole cell.
+ * All launches go to the caller's stream, nothing waits for the device, no atomics: every result
+ * is bit-identical run to run.  n, nq, m < 2^31.  Timed under the profiler's "fusion_points" id
+ * (the list of kernel names is fixed).
+ * ------------------------------------------------------------------------- */
+#define AARMVS_CLOUD_MAX_RINGS 32
+#define AARMVS_CLOUD_AXIS_BITS 21
+typedef struct aarmvs_cloud_nn_args {
+  const float* query;             /* [nq,3] device                                          */
+  const float* target;            /* [m,3] device, sorted by key                            */
+  const long long* target_keys;   /* [m] device, ascending, INT64_MAX entries last          */
+  const int* target_ids;          /* [m] device or NULL (id = position in `target`)         */
+  long long nq, m;                /* 0 <= nq, m < 2^31                                      */
+  double origin[3];               /* the grid: finite                                       */
+  double cell;                    /* finite, > 0                                            */
+  float max_dist;                 /* finite, >= 0; max_dist / cell <= AARMVS_CLOUD_MAX_RINGS */
+  float* dist_out;                /* [nq] device out                                        */
+  int* index_out;                 /* [nq] device out, or NULL                               */
+} aarmvs_cloud_nn_args;
+int aarmvs_cloud_keys(const float* xyz, long long n, const double* origin /* HOST [3] */, double cell,
+                      long long* keys_out, hipStream_t stream);
+int aarmvs_cloud_nn(const aarmvs_cloud_nn_args* args, hipStream_t stream);
+size_t aarmvs_cloud_stats_scratch_bytes(long long n);
+int aarmvs_cloud_stats(const float* dist, long long n, const float* thresholds, int n_thresholds,
+                       double* out, void* scratch, hipStream_t stream);
+size_t aarmvs_cloud_voxel_workspace_bytes(long long n);
+int aarmvs_cloud_voxel_centroids(const float* sorted_xyz, const long long* sorted_keys, long long n,
+                                 float* out_xyz, long long capacity, long long* count, void* workspace,
+                                 hipStream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Epilogue of the evidential head (evidential/models.py:385-459): from the three
  * classifier outputs head[i] = classif_i(...) [1][4][D][H][W] (channels: cost, log nu, log
  * alpha, log beta; at the head's full [maxdisp, H, W] resolution, where get_pred / get_logits'
