@@ -52,6 +52,23 @@ def _ptr(t: torch.Tensor | None) -> int | None:
     return None if t is None else t.data_ptr()
 
 
+def _home(t: torch.Tensor) -> torch.Tensor:
+    """Marks a cached buffer with the stream it was allocated under (``_use`` compares with it)."""
+    t._aarmvs_stream = torch.cuda.current_stream(t.device)
+    return t
+
+
+def _use(t: torch.Tensor) -> torch.Tensor:
+    """A cached buffer about to be used on the current stream.  The caching allocator returns a
+    freed block to the pool of the stream it was allocated under and hands it out again at once
+    there; used under another stream, the buffer is recorded on that stream, so that a block
+    dropped while work is queued on it is reused only after that work."""
+    s = torch.cuda.current_stream(t.device)
+    if s != getattr(t, "_aarmvs_stream", None):   # (a buffer of unknown origin: recorded too)
+        t.record_stream(s)
+    return t
+
+
 def _require_device(*ts: torch.Tensor) -> None:
     for t in ts:
         if not t.is_cuda:
@@ -90,7 +107,7 @@ def pack_params(params: dict, device) -> torch.Tensor:
     packed = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
     check(lib().aarmvs_pack_params(raw.data_ptr(), packed.data_ptr(), _stream()), "pack_params")
     packed._aarmvs_raw = raw  # keep the source alive until the async pack has run
-    return packed
+    return _home(packed)
 
 
 @_on_tensor_device
@@ -659,6 +676,23 @@ class DepthSweep:
     """Runs EMVSNet's depth loop (drmvsnet.py:273-291 / :306-342) on the HIP library.
 
     Holds the packed parameters and a workspace per (B, H, W, nsrc) geometry.
+
+    Streams.  Every call launches on ``torch.cuda.current_stream()`` and is ordered there like a
+    kernel: after what the stream held, before what is enqueued on it next (the library's own
+    streams are forked from it and joined back before the call returns).  The packed parameters
+    are ready on the stream that was current at construction; using the object under another
+    stream needs the caller's ``wait_stream`` first, as for any tensor.  One object serves one
+    stream at a time: it owns one workspace (the recurrent state lives there), so calls on two
+    streams need the caller's ordering between them, and the pieces of one sweep's ``d_range``
+    go to one stream.  Two objects may be in flight on two streams, or in two host threads, at
+    once: the library's unit / backward streams and its aux stream are shared per device, so
+    their work is serialised there and the results do not change.
+
+    The cached buffers (workspace, backward scratch, refine / posterior state: one live geometry
+    at a time) are safe across streams through ``record_stream``: a buffer used under a stream
+    other than the one it was allocated under is recorded on it on every such use, so when a new
+    geometry drops it, the caching allocator reuses the block only after the work queued on it.
+    Nothing is held back by the object itself, which keeps "one live geometry" bounded.
     """
 
     PRECISIONS = {"split": 0, "fp16": 1}  # aarmvs_precision (include/aarmvs.h)
@@ -714,9 +748,9 @@ class DepthSweep:
                                   "(H and W must be multiples of 4, 1 <= nsrc <= 16)")
             self._ws = {k: v for k, v in self._ws.items() if k[0] == "bwd" and k[1:] == key}
             # one live geometry at a time keeps HBM use bounded
-            ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+            ws = _home(torch.empty(n, dtype=torch.uint8, device=self.device))
             self._ws[key] = ws
-        return ws
+        return _use(ws)
 
     def refine_state(self, B, H, W) -> torch.Tensor:
         """The sub-plane refinement's state of a (B, H, W) sweep (16 B per pixel), cached beside
@@ -724,9 +758,9 @@ class DepthSweep:
         key = (B, H, W)
         st = self._refine.get(key)
         if st is None:
-            st = refine_state(B, H * W, self.device)
+            st = _home(refine_state(B, H * W, self.device))
             self._refine = {key: st}
-        return st
+        return _use(st)
 
     def posterior_state(self, B, H, W) -> torch.Tensor:
         """The posterior statistics' state of a (B, H, W) sweep (16 B per pixel), cached beside
@@ -734,9 +768,9 @@ class DepthSweep:
         key = (B, H, W)
         st = self._posterior.get(key)
         if st is None:
-            st = posterior_state(B, H * W, self.device)
+            st = _home(posterior_state(B, H * W, self.device))
             self._posterior = {key: st}
-        return st
+        return _use(st)
 
     def relative(self, ref_proj, src_projs, B: int) -> torch.Tensor:
         """[nsrc,B,12] device tensor of rows 0..2 of src_proj @ inv(ref_proj) per source view
@@ -909,7 +943,7 @@ class DepthSweep:
             a.src_fea[i] = s.data_ptr()
         a.rel_proj = rel.data_ptr()
         a.depth_values = dv.data_ptr()
-        a.packed_params = self.packed.data_ptr()
+        a.packed_params = _use(self.packed).data_ptr()
         a.workspace = ws.data_ptr()
         a.depth_out = _ptr(out["depth"])
         a.conf_out = _ptr(out["conf"])
@@ -1004,8 +1038,9 @@ class DepthSweep:
             n = L.aarmvs_backward_scratch_bytes(B, H, W, nsrc)
             if n == 0:
                 raise AarmvsError(f"aarmvs: invalid backward geometry B={B} H={H} W={W} nsrc={nsrc}")
-            scratch = torch.empty(n, dtype=torch.uint8, device=ref.device)
+            scratch = _home(torch.empty(n, dtype=torch.uint8, device=ref.device))
             self._ws[key] = scratch
+        _use(scratch)
         final = d0 == 0
         grad_ref = torch.empty_like(ref) if final and not regulariser_only else None
         grad_src = [torch.empty_like(t) for t in srcs] if final and not regulariser_only else None
@@ -1029,7 +1064,7 @@ class DepthSweep:
                 a.grad_src[i] = grad_src[i].data_ptr()
         a.rel_proj = rel.data_ptr()
         a.depth_values = dv.data_ptr()
-        a.packed_params = self.packed.data_ptr()
+        a.packed_params = _use(self.packed).data_ptr()
         if (not torch.is_tensor(rel) or tuple(rel.shape) != (nsrc, B, 12) or rel.dtype != torch.float32
                 or rel.device != ref.device or not rel.is_contiguous()):
             raise AarmvsError(f"aarmvs: rel must be a contiguous float32 [nsrc={nsrc}, B={B}, 12] tensor on "
@@ -1095,7 +1130,7 @@ class DepthSweep:
         om = torch.empty(nsrc, B, H, W, device=ref.device) if want_omega else None
         ptrs = (ctypes.c_void_p * nsrc)(*[s.data_ptr() for s in srcs])
         check(lib().aarmvs_cost_slice(ref.data_ptr(), ptrs, rel.data_ptr(), dep.data_ptr(),
-                                      self.packed.data_ptr(), B, C, H, W, nsrc, ws.data_ptr(),
+                                      _use(self.packed).data_ptr(), B, C, H, W, nsrc, ws.data_ptr(),
                                       x.data_ptr(), _ptr(om), _stream()), "cost_slice")
         return x, om
 
@@ -1106,7 +1141,7 @@ class DepthSweep:
         B, C, H, W = x.shape
         ws = self.workspace(B, H, W, nsrc)
         cost = torch.empty(B, 1, H, W, device=x.device)
-        check(lib().aarmvs_unet_step_p(x.data_ptr(), B, H, W, nsrc, step, self.packed.data_ptr(),
+        check(lib().aarmvs_unet_step_p(x.data_ptr(), B, H, W, nsrc, step, _use(self.packed).data_ptr(),
                                        ws.data_ptr(), cost.data_ptr(), self.PRECISIONS[self._precision],
                                        _stream()), "unet_step")
         return cost

@@ -13,6 +13,25 @@
  *     pointer across calls.
  *   - Every launch goes to the caller's stream; no host synchronisation happens
  *     inside any entry point (graph-capturable).
+ *   - Streams and threads.  A call is ordered on `stream` like a kernel: it starts
+ *     after everything `stream` held when it was made, and at return all its work
+ *     (the library's own streams included: they fork from `stream` and join it
+ *     again inside the call) is ordered before whatever is enqueued on `stream`
+ *     next.  Calls may be made from several host threads and on several streams
+ *     of one device at once, provided each has its own workspace, record, scratch
+ *     and state buffers (parameters and inputs may be shared: they are only read).
+ *     The library's unit / backward streams and the aux stream are shared per
+ *     device: concurrent callers' units are serialised on them, and the results do
+ *     not change (every schedule is bit-identical).  The events are per thread (and
+ *     device), re-recorded call after call; a wait is bound to the record enqueued
+ *     before it, so one thread may alternate between callers' streams.
+ *     aarmvs_last_error() is per thread.  aarmvs_profile_* is for one caller at a
+ *     time (one global table of events, without a lock).  The pieces of
+ *     one sweep's d_range, and the calls of one backward chain, share a workspace:
+ *     issue them on one stream, or order them yourself.  With more than four
+ *     streams in the process, streams share hardware queues: work on one stream
+ *     then also waits for what its queue partner holds (slower, never wrong).
+ *     tests/test_gpu_streams.py holds the library to this paragraph.
  *   - Return 0 on success, a nonzero aarmvs_status otherwise; the message is in
  *     aarmvs_last_error() (thread-local).  Shapes are validated before launch.
  *   - Constraints (from the reference's own shape rules): C == 32 feature

@@ -3,7 +3,12 @@
 // that every pair of conflicting buffer accesses is ordered, that every event wait resolves to
 // the record it means, and that every call ends with all its work ordered on the caller's
 // stream.  It proves ordering of the buffers modelled here (the reads and writes of
-// launch_unet_step, launch_head_wta and the cost stage); it says nothing about the runtime.
+// launch_unet_step, launch_head_wta and the cost stage); it says nothing about the runtime
+// (tests/test_gpu_streams.py runs the same scenarios on the device).
+//
+// Two sweeps in flight (check_two_sweeps): two callers with their own buffers and their own
+// streams issue their calls alternately from one host thread, so that the library's streams and
+// ONE event array serve both.  Each sweep must still pass every check above.
 //
 // Happens-before: each stream keeps the set of ops known complete before its next launch; a
 // launch inherits the set and joins it; a record snapshots the set; a wait merges the snapshot
@@ -19,7 +24,8 @@ using namespace aarmvs;
 
 namespace {
 
-constexpr int kD = 40, kMaxOps = 512, kPhys = 6, kK = 48;   // kK > kD + 1: per-plane buffer indices
+constexpr int kD = 40, kMaxOps = 1024, kPhys = 7, kK = 48;   // kK > kD + 1: per-plane buffer indices
+constexpr int kCallerB = 6;   // the second caller's stream (two sweeps in flight)
 using Set = std::bitset<kMaxOps>;
 
 // buffer ids: per-cell [5][kK], per-plane [kK], then the single buffers
@@ -48,25 +54,36 @@ int g_failed = 0;
     }                                                         \
   } while (0)
 
-// One sweep (one or more calls) on simulated streams.
+// One sweep (one or more calls) on simulated streams; or two sweeps, each with its caller's
+// stream and (unless told to share) its buffer set, on the same library streams and events.
 struct Sim {
   bool record_model;   // a training record: per-plane slabs for x, h, c, u, stats, t1, omega stats
   bool alias;          // the caller's aux stream is library stream 4
   const SweepPlan* plan = nullptr;
   int d_begin = 0, call = -1, gi = 0, last_u = 0, last_d = 0;
-  int nops = 0, op_phys[kMaxOps] = {};
+  int nops = 0, op_phys[kMaxOps] = {}, op_owner[kMaxOps] = {};
+  int caller = 0, owner = 0;   // the current call's caller stream and sweep
   Set done[kPhys];
   struct Ev { Set snap; Tag tag; int call = -1; } ev[kSweepEvents];
-  struct BufState { int writer = -1; Set readers; } bufs[kBufs];
+  struct BufState { int writer = -1; Set readers; } sets[2][kBufs];
+  BufState* bufs = sets[0];
   struct Pending { int ev; Tag tag; } pend[8];
   int npend = 0;
   int hazards = 0, event_errors = 0;
 
   Sim(bool rec, bool al) : record_model(rec), alias(al) {}
 
+  // the calls that follow belong to `sweep`, issued on caller stream `stream`
+  void use(int sweep, int stream, bool rec, bool shared_bufs) {
+    owner = sweep;
+    caller = stream;
+    record_model = rec;
+    bufs = sets[shared_bufs ? 0 : sweep];
+  }
+
   int phys(int slot) {
     switch (plan->slot[slot]) {
-      case kCaller: return 0;
+      case kCaller: return caller;
       case kCallerAux: return alias ? 5 : 1;
       case kLib1: return 2;
       case kLib2: return 3;
@@ -85,6 +102,7 @@ struct Sim {
     const int op = nops++;
     if (op >= kMaxOps) { std::printf("too many ops\n"); std::exit(2); }
     op_phys[op] = p;
+    op_owner[op] = owner;
     return op;
   }
   void finish(int op) { done[op_phys[op]].set(op); }
@@ -135,7 +153,7 @@ struct Sim {
     ++call;
     npend = 0;
     if (d0 == 0) {   // the memsets and c8 copies, on the caller's stream
-      const int op = launch(0);
+      const int op = launch(caller);
       for (int k = 0; k < 5; ++k) {
         for (int e = 0; e < (record_model ? 1 : kHRing[k]); ++e) wr(op, h(k, e));
         wr(op, c(k, 0));
@@ -148,16 +166,16 @@ struct Sim {
     const int rc = walk_sweep(p, d0, d1, d1 - 1, s);
     if (!rc) {
       CHECK(npend == 0, "waits left without their launch");
-      const int op = launch(0);   // finalize
+      const int op = launch(caller);   // finalize
       rd(op, B_WTA);
       finish(op);
     }
     return rc;
   }
-  // ops not ordered on the caller's stream, those of stream `except` aside
+  // the current sweep's ops not ordered on its caller's stream, those of stream `except` aside
   int count_unjoined(int except = -1) const {
     int n = 0;
-    for (int op = 0; op < nops; ++op) n += !done[0][op] && op_phys[op] != except;
+    for (int op = 0; op < nops; ++op) n += op_owner[op] == owner && !done[caller][op] && op_phys[op] != except;
     return n;
   }
 
@@ -172,13 +190,13 @@ struct Sim {
     done[p] |= ev[i].snap;
   }
   int fork(int slot, int i) {
-    do_record(0, i, {E_FORK, 0, 0});
+    do_record(caller, i, {E_FORK, 0, 0});
     do_wait(phys(slot), i);
     return 0;
   }
   int join(int slot, int i) {
     do_record(phys(slot), i, {E_FORK, 0, 0});
-    do_wait(0, i);
+    do_wait(caller, i);
     return 0;
   }
   int record(int slot, int i) {
@@ -218,14 +236,14 @@ struct Sim {
     return 0;
   }
   int slice_copy(const SweepGroup& g, int d) {
-    const int op = launch(0);
+    const int op = launch(caller);
     rd(op, x(g, d));
     finish(op);
     return 0;
   }
   int step(const SweepGroup& g, int d) {
     if (npend) ++event_errors;
-    const int op = launch(0);
+    const int op = launch(caller);
     for (int u = 0; u < kUnetUnits; ++u) unit_acc(op, u, g, d);
     head_acc(op, d);
     finish(op);
@@ -307,6 +325,7 @@ struct Case {
   SweepOverrides o;
 };
 SweepPlan plan_of(const Case& c) { return plan_sweep(c.aux, c.capturing, c.recording, c.px, c.o); }
+SweepOpt opt(long v) { return SweepOpt{true, v}; }
 
 bool uses(const SweepPlan& p, SweepStream id) {
   for (SweepStream s : p.slot)
@@ -328,6 +347,53 @@ int run_sweep(const Case& c, const int* cut, bool alias, int drop, long* runs) {
   }
   ++*runs;
   return sim->hazards + (drop == W_NONE ? sim->event_errors + bad : 0);
+}
+
+// Two sweeps in flight from one host thread: sweep 0 on caller stream 0, sweep 1 on kCallerB, the
+// pieces of the two issued alternately.  Both callers' aux stream is the library's (alias), the
+// library streams and the event array are the same for both; each has its buffer set unless
+// shared_bufs (the use the contract forbids: it must show as a hazard).
+int run_two_sweeps(const Case& ca, const Case& cb, const int* cut, bool shared_bufs, long* runs) {
+  auto sim = std::make_unique<Sim>(false, true);
+  int bad = 0;
+  for (int i = 0; cut[i + 1] >= 0; ++i)
+    for (int w = 0; w < 2; ++w) {
+      const Case& c = w ? cb : ca;
+      sim->use(w, w ? kCallerB : 0, c.recording, shared_bufs);
+      const SweepPlan p = plan_of(c);   // per call, as aarmvs_sweep does
+      bad += sim->run_call(p, cut[i], cut[i + 1], *sim) != 0;
+      bad += sim->count_unjoined();     // the call ends joined on its own caller's stream
+    }
+  ++*runs;
+  return sim->hazards + sim->event_errors + bad;
+}
+
+// every default plan beside itself and beside the plain small-frame sweep (an eval sweep next to
+// a training forward among them), every cut
+void check_two_sweeps(long* runs) {
+  const long npl[4] = {0, 1, 3, 16};
+  const Case partner{true, false, false, 160L * 128, {}};
+  for (int bits = 0; bits < 16; ++bits)
+    for (int streams = 0; streams <= 5; ++streams)
+      for (long n : npl) {
+        Case c{(bits & 1) != 0, (bits & 2) != 0, (bits & 4) != 0, (bits & 8) ? 160L * 128 : 1600L * 1184, {}};
+        if (streams) c.o.reg_streams = c.o.reg_streams_rec = opt(streams);
+        if (n) c.o.npl = opt(n);
+        for (const auto& cut : kCuts)
+          for (int other = 0; other < 2; ++other) {
+            const int bad = run_two_sweeps(c, other ? partner : c, cut, false, runs);
+            CHECK(bad == 0, "two sweeps: %d unordered accesses / event errors / unjoined ops (bits %d streams %d npl %ld, "
+                  "cut %d.., partner %d)", bad, bits, streams, n, cut[1], other);
+          }
+      }
+  // not vacuous: the same two sweeps on ONE buffer set race, under both default plans
+  for (long px : {160L * 128, 1600L * 1184}) {
+    const Case c{true, false, false, px, {}};
+    long unused = 0;
+    const int n = run_two_sweeps(c, c, kCuts[1], true, &unused);
+    std::printf("two sweeps on one buffer set (%ld px): %d hazards\n", px, n);
+    CHECK(n > 0, "two sweeps sharing their buffers go unnoticed (%ld px)", px);
+  }
 }
 
 // every cut, with the caller's aux stream distinct from library stream 4 and equal to it
@@ -352,8 +418,6 @@ void map_text(int m, char (&s)[6]) {   // m in 0 .. 624: units 1..4 in base 5, u
   for (int u = 4; u >= 1; --u, m /= 5) s[u] = char('0' + m % 5);
   s[5] = 0;
 }
-
-SweepOpt opt(long v) { return SweepOpt{true, v}; }
 
 void check_all_maps(long* runs) {
   // the map applies once a call has more than one unit stream: with an aux stream (large frame:
@@ -512,6 +576,7 @@ int main() {
   check_plans();
   check_all_maps(&runs);
   check_defaults(&runs);
+  check_two_sweeps(&runs);
   check_join_on_error();
   check_not_vacuous();
   std::printf("sweep_schedule_check: %ld sweeps simulated, %d failed checks\n", runs, g_failed);

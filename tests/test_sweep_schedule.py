@@ -4,7 +4,9 @@ tests/sweep_schedule_check.cpp is a stand-alone host program that includes only 
 it walks the plan of every unit -> stream map (and of the default plans) with a recording
 sink, simulates happens-before between streams and events, and fails on a pair of conflicting
 buffer accesses left unordered, on an event wait that resolves to another record than the one
-it means, or on a call that returns with work not ordered on the caller's stream.  It also
+it means, or on a call that returns with work not ordered on the caller's stream; the same for
+two sweeps with their own buffers and caller streams whose calls alternate on the shared library
+streams and one event array (and two sweeps on ONE buffer set must race).  It also
 shows itself not vacuous: with all waits of one class dropped, some map must race.  Built with
 AddressSanitizer and UBSan, like tools/asan/abi_host.cpp; no GPU, nothing loaded into Python.
 """
