@@ -94,13 +94,22 @@ def relative_projection(src_proj: torch.Tensor, ref_proj: torch.Tensor) -> torch
     return torch.matmul(s, torch.inverse(r))[:, :3, :4].contiguous()
 
 
-@_on_tensor_device
 def pack_params(params: dict, device) -> torch.Tensor:
-    """Flatten the 48 sweep tensors (checkpoint keys) and pack them on the device."""
+    """Flatten the sweep tensors (checkpoint keys) and pack them on the device."""
     missing = [k for k in SWEEP_KEYS if k not in params]
     if missing:
         raise KeyError(f"aarmvs.pack_params: missing parameters {missing[:3]}...")
-    raw = torch.cat([params[k].detach().reshape(-1).float() for k in SWEEP_KEYS]).to(device)
+    return pack_flat([params[k] for k in SWEEP_KEYS], device)
+
+
+@_on_tensor_device
+def pack_flat(tensors, device) -> torch.Tensor:
+    """``pack_params`` of the sweep tensors given in SWEEP_KEYS order: a NEW packed buffer holding
+    their values as of this call on the current stream (one concatenation and one pack kernel,
+    both asynchronous; later in-place changes to the tensors do not reach it).  EMVSNet calls
+    this on every forward, so the per-tensor host work is one reshape each."""
+    with torch.no_grad():
+        raw = torch.cat([t.reshape(-1) for t in tensors]).to(device, torch.float32)
     if raw.numel() != lib().aarmvs_param_count():
         raise AarmvsError("aarmvs.pack_params: parameter count mismatch with libaarmvs")
     nbytes = lib().aarmvs_packed_param_bytes()
@@ -738,6 +747,16 @@ class DepthSweep:
         elif not on:
             self._aux = None
 
+    def _packed_arg(self, packed) -> torch.Tensor:
+        """``self.packed``, or a caller's ``pack_params`` buffer after checking it (the kernels read
+        aarmvs_packed_param_bytes from it without bounds)."""
+        if packed is None:
+            return self.packed
+        if (not torch.is_tensor(packed) or packed.dtype != torch.float32 or packed.device != self.device
+                or not packed.is_contiguous() or packed.numel() * 4 < lib().aarmvs_packed_param_bytes()):
+            raise AarmvsError(f"aarmvs: packed must be a pack_params buffer on {self.device}")
+        return packed
+
     def workspace(self, B, H, W, nsrc) -> torch.Tensor:
         key = (B, H, W, nsrc)
         ws = self._ws.get(key)
@@ -868,8 +887,13 @@ class DepthSweep:
     @_on_tensor_device
     def __call__(self, ref_fea, src_feas, ref_proj, src_projs, depth_values, *,
                  want_depth=True, want_cost=False, d_range=None, debug=False, cost_out=None,
-                 rel=None, record=None, record_d0=0, want_refined=False, want_posterior=False):
+                 rel=None, record=None, record_d0=0, want_refined=False, want_posterior=False,
+                 packed=None):
         """Returns dict(depth, conf, cost, slice, omega) (entries None when not requested).
+
+        ``packed``: a ``pack_params`` buffer to run on instead of ``self.packed`` (an autograd
+        graph passes the buffer of its own forward to the checkpoint recompute, whatever the
+        object holds by then).
 
         ``want_refined`` (opt-in, inference only) adds ``depth_refined`` and ``conf_window``
         [B,H,W] and ``index`` [B,H,W] int32: the local expectation of depth over the winning
@@ -943,7 +967,8 @@ class DepthSweep:
             a.src_fea[i] = s.data_ptr()
         a.rel_proj = rel.data_ptr()
         a.depth_values = dv.data_ptr()
-        a.packed_params = _use(self.packed).data_ptr()
+        packed = self._packed_arg(packed)
+        a.packed_params = _use(packed).data_ptr()
         a.workspace = ws.data_ptr()
         a.depth_out = _ptr(out["depth"])
         a.conf_out = _ptr(out["conf"])
@@ -990,12 +1015,13 @@ class DepthSweep:
         if posterior is not None:
             opts.posterior = ctypes.pointer(posterior)
         check(lib().aarmvs_sweep_ex(ctypes.byref(a), ctypes.byref(opts), _stream()), "sweep")
-        out["_keepalive"] = (rel, dv, srcs, ref, rec_struct)
+        out["_keepalive"] = (rel, dv, srcs, ref, rec_struct, packed)
         return out
 
     @_on_tensor_device
     def backward(self, ref_fea, src_feas, rel, depth_values, record, grad_cost, *,
-                 regulariser_only=False, want_grad_x=False, d_range=None, record_d0=0, grad_x_out=None):
+                 regulariser_only=False, want_grad_x=False, d_range=None, record_d0=0, grad_x_out=None,
+                 packed=None):
         """Backward of a recorded training sweep (aarmvs_sweep_backward): from dL/dcost
         [B,D,H,W] to (grad_ref [B,32,H,W], [grad_src [B,32,H,W]] per view, {sweep parameter
         name: gradient}, grad_x [D,B,H,W,32] NHWC or None).  ``regulariser_only`` stops after
@@ -1008,7 +1034,9 @@ class DepthSweep:
         segment may use this object in between.  The calls before the final one return None; the
         final one (d0 == 0) returns the gradients of the whole sweep, bit for bit those of one
         call on a whole record.  ``grad_x_out``: a caller-owned [D,B,H,W,32] buffer for grad_x
-        (each call fills its planes)."""
+        (each call fills its planes).  ``packed``: the ``pack_params`` buffer the recorded forward
+        ran on, when that is no longer ``self.packed`` (a graph differentiates at its own
+        forward's weights)."""
         ref = ref_fea.contiguous()
         srcs = [t.contiguous() for t in src_feas]
         _require_device(ref, *srcs, grad_cost)
@@ -1064,7 +1092,7 @@ class DepthSweep:
                 a.grad_src[i] = grad_src[i].data_ptr()
         a.rel_proj = rel.data_ptr()
         a.depth_values = dv.data_ptr()
-        a.packed_params = _use(self.packed).data_ptr()
+        a.packed_params = _use(self._packed_arg(packed)).data_ptr()
         if (not torch.is_tensor(rel) or tuple(rel.shape) != (nsrc, B, 12) or rel.dtype != torch.float32
                 or rel.device != ref.device or not rel.is_contiguous()):
             raise AarmvsError(f"aarmvs: rel must be a contiguous float32 [nsrc={nsrc}, B={B}, 12] tensor on "

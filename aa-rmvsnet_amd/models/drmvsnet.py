@@ -212,7 +212,9 @@ class _SweepTrain(torch.autograd.Function):
     backward is aarmvs_sweep_backward on that record (the recurrence's reverse sweep, the
     cost-slice / omega / warp backward and every parameter gradient, drmvsnet.py:273-291
     differentiated).  The record is saved with save_for_backward, so autograd frees it after
-    the backward and a second backward through a freed graph raises autograd's own error."""
+    the backward and a second backward through a freed graph raises autograd's own error.  So is
+    the packed parameter buffer the forward ran on (``sweep.packed`` at that time): the backward
+    differentiates at the forward's weights, whatever the parameters hold by then."""
 
     @staticmethod
     def forward(ctx, model, sweep, ref_proj, src_projs, depth_values, ref, *rest):
@@ -223,12 +225,14 @@ class _SweepTrain(torch.autograd.Function):
         cost = torch.empty(B, D, H, W, device=ref.device)
         rel = sweep.relative(ref_proj, src_projs, B)
         rec = sweep.record_buffers(B, H, W, D, ref.device, nsrc=nsrc)
+        packed = sweep.packed
         sweep(ref, srcs, ref_proj, src_projs, depth_values, want_depth=False, cost_out=cost,
-              rel=rel, record=rec)
+              rel=rel, record=rec, packed=packed)
         ctx.sweep = sweep
         ctx.nsrc = nsrc
         ctx.nparams = len(params)
-        ctx.save_for_backward(ref, *srcs, rel, depth_values, *(rec[k] for k in _ops.DepthSweep.RECORD_KEYS))
+        ctx.save_for_backward(ref, *srcs, rel, depth_values, packed,
+                              *(rec[k] for k in _ops.DepthSweep.RECORD_KEYS))
         return cost
 
     @staticmethod
@@ -237,9 +241,9 @@ class _SweepTrain(torch.autograd.Function):
         saved = ctx.saved_tensors
         nsrc = ctx.nsrc
         ref, srcs = saved[0], list(saved[1:1 + nsrc])
-        rel, dv = saved[1 + nsrc], saved[2 + nsrc]
-        rec = dict(zip(_ops.DepthSweep.RECORD_KEYS, saved[3 + nsrc:]))
-        g_ref, g_srcs, g_par, _ = ctx.sweep.backward(ref, srcs, rel, dv, rec, grad_cost)
+        rel, dv, packed = saved[1 + nsrc], saved[2 + nsrc], saved[3 + nsrc]
+        rec = dict(zip(_ops.DepthSweep.RECORD_KEYS, saved[4 + nsrc:]))
+        g_ref, g_srcs, g_par, _ = ctx.sweep.backward(ref, srcs, rel, dv, rec, grad_cost, packed=packed)
         g_params = [g_par[k] for k in _ops.SWEEP_KEYS]
         return (None, None, None, None, None, g_ref, *g_srcs, *g_params)
 
@@ -282,10 +286,11 @@ class _SweepTrainCkpt(torch.autograd.Function):
         rel = sweep.relative(ref_proj, src_projs, B)
         rec = sweep.record_buffers(B, H, W, D, ref.device, nsrc=nsrc, planes=min(S, D))
         slab = sweep.record_bytes(B, H, W, 1, nsrc=nsrc)[1]
+        packed = sweep.packed   # (saved: recompute and backward run at this forward's weights)
         ckpts = []   # ckpts[i - 1]: the state before segment i
         for s0, s1 in segs:
             sweep(ref, srcs, ref_proj, src_projs, depth_values, want_depth=False, cost_out=cost,
-                  rel=rel, record=rec, record_d0=s0, d_range=(s0, s1))
+                  rel=rel, record=rec, record_d0=s0, d_range=(s0, s1), packed=packed)
             if s1 < D:
                 ckpts.append(rec["state"][(s1 - s0) * slab:(s1 - s0 + 1) * slab].clone())
                 rec["state"][:slab].copy_(ckpts[-1])
@@ -294,7 +299,7 @@ class _SweepTrainCkpt(torch.autograd.Function):
         ctx.segs = segs
         ctx.slab = slab
         ctx.holds = len(segs) - 1
-        ctx.save_for_backward(ref, *srcs, rel, depth_values, *ckpts,
+        ctx.save_for_backward(ref, *srcs, rel, depth_values, packed, *ckpts,
                               *(rec[k] for k in _ops.DepthSweep.RECORD_KEYS))
         return cost
 
@@ -304,10 +309,10 @@ class _SweepTrainCkpt(torch.autograd.Function):
         saved = ctx.saved_tensors
         nsrc, segs, slab, sweep = ctx.nsrc, ctx.segs, ctx.slab, ctx.sweep
         ref, srcs = saved[0], list(saved[1:1 + nsrc])
-        rel, dv = saved[1 + nsrc], saved[2 + nsrc]
+        rel, dv, packed = saved[1 + nsrc], saved[2 + nsrc], saved[3 + nsrc]
         nck = len(segs) - 1
-        ckpts = saved[3 + nsrc:3 + nsrc + nck]
-        rec = dict(zip(_ops.DepthSweep.RECORD_KEYS, saved[3 + nsrc + nck:]))
+        ckpts = saved[4 + nsrc:4 + nsrc + nck]
+        rec = dict(zip(_ops.DepthSweep.RECORD_KEYS, saved[4 + nsrc + nck:]))
         grad_cost = grad_cost.contiguous()
         out = None
         for i in range(len(segs) - 1, -1, -1):
@@ -317,9 +322,10 @@ class _SweepTrainCkpt(torch.autograd.Function):
                 if i > 0:
                     _raw_copy(rec["state"][:slab], ckpts[i - 1])
                 sweep(ref, srcs, None, [None] * nsrc, dv, want_depth=False, rel=rel, record=rec,
-                      record_d0=s0, d_range=(s0, s1))
+                      record_d0=s0, d_range=(s0, s1), packed=packed)
                 ctx.holds = i
-            out = sweep.backward(ref, srcs, rel, dv, rec, grad_cost, d_range=(s0, s1), record_d0=s0)
+            out = sweep.backward(ref, srcs, rel, dv, rec, grad_cost, d_range=(s0, s1), record_d0=s0,
+                                 packed=packed)
         g_ref, g_srcs, g_par, _ = out
         g_params = [g_par[k] for k in _ops.SWEEP_KEYS]
         return (None, None, None, None, None, None, g_ref, *g_srcs, *g_params)
@@ -400,14 +406,32 @@ class EMVSNet(nn.Module):
         self.return_cost = return_cost
         self._sweep_cache = None
 
-    # -- HIP sweep object, repacked whenever a sweep parameter changed ---------------
+    # -- HIP sweep object ----------------------------------------------------------
     def _sweep(self, device) -> _ops.DepthSweep:
+        """The device's DepthSweep with the sweep parameters' current values packed into a NEW
+        buffer (two asynchronous launches, no host synchronisation).  Every call repacks: no
+        version counter or data pointer sees ``p.data.mul_()`` or a write through a tensor that
+        aliases the parameters, so nothing is inferred from them.  Only the object (its
+        workspaces, its stream) is cached; the buffer of an earlier forward is never rewritten
+        and stays with the autograd graph that saved it."""
         params = _sweep_params(self)
-        key = (str(device), tuple((p.data_ptr(), p._version) for p in params))
-        if self._sweep_cache is None or self._sweep_cache[0] != key:
-            sw = _ops.DepthSweep({k: p.detach() for k, p in zip(_ops.SWEEP_KEYS, params)}, device)
-            self._sweep_cache = (key, sw)
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:   # (tensors always carry the index)
+            device = torch.device("cuda", torch.cuda.current_device())
+        cache = self._sweep_cache
+        if cache is None or cache[0] != device:
+            self._sweep_cache = (device, _ops.DepthSweep(dict(zip(_ops.SWEEP_KEYS, params)), device))
+        else:
+            cache[1].packed = _ops.pack_flat(params, device)
         return self._sweep_cache[1]
+
+    def __getstate__(self):
+        """copy.deepcopy, pickle and torch.save(model) go through here: the DepthSweep (device
+        workspaces, a stream handle) is not part of a model's state and is rebuilt on the next
+        forward, so a copy shares nothing with the original."""
+        state = self.__dict__.copy()
+        state["_sweep_cache"] = None
+        return state
 
     def _check_geometry(self, H, W):
         reg = self.cost_regularization
