@@ -146,7 +146,7 @@ struct CostArgs {
   const float* depth_values;  // [B,D]
   const float* params;    // packed
 };
-// The cost-slice stage (warp_cost.hip) for the planes d0 .. d0 + n - 1 (n <= kPlaneGroup):
+// The cost-slice stage (cost_fwd.hip) for the planes d0 .. d0 + n - 1 (n <= kPlaneGroup):
 // omega_group clears the group's statistics, then writes t1 and the three GroupNorm
 // statistics of every plane (omega conv + omega_stats<1> + <2>); cost_x_group then writes
 // each plane's cost slice to x0 + k ws.x_plane (and, for plane omega_k, the omega weights
@@ -421,7 +421,7 @@ enum KernelId : int {
   K_CELL0, K_CELL1, K_CELL2, K_CELL3, K_CELL4,
   K_DECONV0, K_DECONV1, K_HEAD_WTA, K_FINALIZE, K_SOFTMAX, K_WARP, K_TO_C8, K_STAT_REDUCE,
   K_GN_REDUCE, K_EVIDENTIAL,
-  // the training backward (bptt.hip, the cbw_* kernels of warp_cost.hip)
+  // the training backward (bptt.hip, the cbw_* kernels of cost_bwd.hip)
   K_GATE_BWD0, K_GATE_BWD1, K_GATE_BWD2, K_GATE_BWD3, K_GATE_BWD4,
   K_DGRAD0, K_DGRAD1, K_DGRAD2, K_DGRAD3, K_DGRAD4,
   K_WGRAD0, K_WGRAD1, K_WGRAD2, K_WGRAD3, K_WGRAD4,

@@ -1,5 +1,5 @@
 """Cases for the kernels that turn a cost volume into what the user sees -- ops.softmax_depth,
-the standalone ops.wta_update and ops.evidential_epilogue (csrc/convlstm.hip softmax_depth_kernel
+the standalone ops.wta_update and ops.evidential_epilogue (csrc/depth_head.hip softmax_depth_kernel
 and wta_update_kernel, csrc/evidential.hip) -- with their references, and the one frame that
 reaches the second stride of the launchers that cap their grid at 4096 blocks of 256 threads.
 

@@ -14,7 +14,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-# the cost-slice backward's tile logic (warp_cost.hip cbw_feat_kernel): kFbT, the tile edge in
+# the cost-slice backward's tile logic (cost_bwd.hip cbw_feat_kernel): kFbT, the tile edge in
 # reference pixels; kFbBoxPx, the largest source box a block owns; kFbSlots, the reference
 # pixels a box cell (a top-left tap position) holds per plane.  bptt.hip's kPlaneGroup is PLANES.
 TILE = 16

@@ -331,7 +331,7 @@ def test_backward_is_deterministic_in_the_parameter_gradients():
     """Two backward calls agree bit for bit: the parameter gradients are fixed-order fp64 sums,
     dL/dref a fixed-order sum over views, and dL/dsrc (grid_sample's scatter, whose
     contributions reach a source pixel from many blocks) a 64-bit fixed-point sum
-    (warp_cost.hip to_fixed: integer atomics are associative)."""
+    (cost_bwd.hip to_fixed: integer atomics are associative)."""
     B, N, H, W, D = 1, 3, 32, 48, 4
     sc, P, feats, proj, dv, sw, args = _setup(B, N, H, W, D, 9, 2)
     cost, rec, rel = _record_forward(sw, args, B, H, W, D)

@@ -74,7 +74,7 @@ def _scale_base_tensors():
 
 def test_standalone_warp_backward_over_cotangent_scale():
     """aarmvs_homo_warp_backward sums dL/dsrc in the same 64-bit fixed point as the sweep's
-    backward, with its own exponent (warp_cost.hip warp_bwd_exp): grad_out * 2^k for k = -96 ..
+    backward, with its own exponent (warp.hip warp_bwd_exp): grad_out * 2^k for k = -96 ..
     +96 on the scale cases' scene, against float64 autograd through the oracle's warp within
     max(2e-5, 2 x float32 grid_sample's own error) relative L2; for k = -48, +48, +96 also
     bit-identical to the k = 0 result after rescaling (a power-of-two scale only moves the

@@ -2,7 +2,7 @@
 (tests/geometry_cases.py), against the CPU oracle and its float64 autograd.
 
 Every other GPU test draws its cameras from aarmvs.synthetic.scene: one fronto-parallel rig and
-one depth list broadcast over the batch.  There the cost-slice backward (warp_cost.hip
+one depth list broadcast over the batch.  There the cost-slice backward (cost_bwd.hip
 cbw_feat_kernel) only ever takes its in-box gather, and no index of the form
 ``Rel + 12 * (v * B + b)`` or ``dvals[b * D + d]`` can be told from its b = 0 value.  Here:
 

@@ -1,6 +1,6 @@
 """Which backward scratch region is read before it is written (the first-call difference found
 by tools/bwd_nondet.py: run 0 of a process differs, runs 1.. agree)?  For each region of the
-backward scratch (bptt.hip BpttLayout, then warp_cost.hip CostBwdLayout) the whole scratch is
+backward scratch (bptt.hip BpttLayout, then cost_bwd.hip CostBwdLayout) the whole scratch is
 zeroed, that region filled with NaN bytes, and the backward run once: a region whose NaNs reach
 dL/dref, dL/dx or the parameter gradients is read before this run writes it."""
 import os

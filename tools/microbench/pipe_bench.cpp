@@ -2,7 +2,7 @@
 // headline geometry (1600x1184, 6 source views).  Includes the kernel source; links
 // libaarmvs.so for the parameter layout / workspace carve.  Not shipped; numbers are
 // for design decisions.
-#include "../../aa-rmvsnet_amd/csrc/warp_cost.hip"
+#include "../../aa-rmvsnet_amd/csrc/cost_fwd.hip"
 
 #include <cstdio>
 #include <cstring>
@@ -169,6 +169,9 @@ int main(int argc, char** argv) {
     }
     // plane npl-1 must equal a single-plane launch at d_next = npl
     if (npl > 1) {
+      // (again: at npl = 8 the ablations above wrote t1b last)
+      om();
+      CK(hipDeviceSynchronize());
       std::vector<float4> hb(t1k), hs(t1k);
       CK(hipMemcpy(hb.data(), t1b + (npl - 1) * t1k, t1k * 16, hipMemcpyDeviceToHost));
       PipeArgs a1 = a; a1.npl = 1; a1.d_next = npl;
