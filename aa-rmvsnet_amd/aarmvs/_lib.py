@@ -173,6 +173,24 @@ class CloudNnArgs(ctypes.Structure):
     ]
 
 
+class CloudThinArgs(ctypes.Structure):
+    """Mirror of ``aarmvs_cloud_thin_args``."""
+    _fields_ = [
+        ("xyz", c_void_p),
+        ("keys", c_void_p),
+        ("rank", c_void_p),
+        ("n", c_longlong),
+        ("origin", c_double * 3),
+        ("cell", c_double),
+        ("r", ctypes.c_float),
+        ("init", c_int),
+        ("which", c_int),
+        ("state", c_void_p * 2),
+        ("remaining", c_void_p),
+        ("scratch", c_void_p),
+    ]
+
+
 # name -> (restype, argtypes)
 SIGNATURES = {
     "aarmvs_last_error": (c_char_p, []),
@@ -240,6 +258,11 @@ SIGNATURES = {
     "aarmvs_cloud_voxel_workspace_bytes": (c_size_t, [c_longlong]),
     "aarmvs_cloud_voxel_centroids": (c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_longlong, c_void_p,
                                              c_void_p, c_void_p]),
+    "aarmvs_cloud_thin_scratch_bytes": (c_size_t, [c_longlong]),
+    "aarmvs_cloud_thin": (c_int, [ctypes.POINTER(CloudThinArgs), c_int, c_void_p]),
+    "aarmvs_cloud_regions": (c_int, [c_void_p, c_longlong, c_void_p, ctypes.POINTER(c_int),
+                                     ctypes.POINTER(c_double), c_double, c_double, ctypes.POINTER(c_double),
+                                     c_void_p, c_void_p]),
     "aarmvs_evidential_epilogue": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int, c_void_p,
                                            c_void_p, c_void_p]),
     "aarmvs_evidential_epilogue_backward": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int,

@@ -2,12 +2,16 @@
 nearest-neighbour distances between two clouds, voxel down-sampling, and the plain accuracy /
 completeness (DTU-style) and precision / recall / F-score (Tanks-and-Temples-style) figures.
 
-NOT the official protocols: DTU's observation masks, ground-plane cut and ``reducePts`` and Tanks
-and Temples' alignment and cropping need dataset files and are out of scope.  Sorting is
-``torch.sort`` (plumbing); the keys, the query, the statistics and the centroids are HIP kernels,
-and there is no CPU fallback: CPU tensors are refused.
+``evaluate_dtu`` adds the DTU protocol (include/aarmvs.h, "DTU protocol"):
+``reducePts`` as ``thin`` (the greedy walk run as parallel rounds), the observation mask and the
+ground-plane cut as ``regions``, from the scan's ``ObsMask`` / ``Plane`` files.  NOT implemented:
+Tanks and Temples' alignment and cropping, which need that dataset's files.  Sorting is
+``torch.sort`` (plumbing); the keys, the query, the statistics, the centroids, the thinning rounds
+and the region flags are HIP kernels, and there is no CPU fallback: CPU tensors are refused.
 
     python -m aarmvs.cloud_eval --recon A.ply --gt B.ply --max_dist 20 --tau 1 2 5 [--voxel V] [--json out.json]
+    python -m aarmvs.cloud_eval --protocol dtu --recon A.ply --gt stl.ply --obs_mask M.mat --plane P.mat
+                                [--thin 0.2 --patch 60 --max_dist 20 --seed 0 --json out.json]
 """
 from __future__ import annotations
 
@@ -233,6 +237,202 @@ def evaluate(recon, gt, max_dist, thresholds=(), voxel=None):
 
 
 # ---------------------------------------------------------------------------------
+# The DTU protocol (include/aarmvs.h, "DTU protocol")
+# ---------------------------------------------------------------------------------
+IN_BOX, IN_OBS, ABOVE = 1, 2, 4
+
+
+def _ranks(order, seed, n):
+    """The int32 [n] ranks of ``thin``: a seeded permutation, the input order, or the caller's own."""
+    if isinstance(order, str):
+        if order == "random":
+            return torch.from_numpy(np.random.default_rng(seed).permutation(n).astype(np.int32))
+        if order == "input":
+            return torch.arange(n, dtype=torch.int32)
+        raise ValueError('aarmvs: order must be "random", "input" or an int32 rank tensor')
+    rank = torch.as_tensor(order)
+    if rank.dtype != torch.int32 or rank.dim() != 1 or rank.shape[0] != n:
+        raise ValueError("aarmvs: the ranks must be an int32 [n] tensor")
+    if torch.unique(rank).shape[0] != n:
+        raise ValueError("aarmvs: the ranks must be distinct")
+    return rank
+
+
+def thin(xyz, radius, order="random", seed=0, rounds_per_call=8):
+    """DTU's ``reducePts``: walk the points in ascending rank, keep a point, drop every point within
+    ``radius`` of it (inclusive).  Returns (kept_index int64 [n'] ascending, in the caller's order;
+    the number of rounds to the fixpoint).  ``order``: "random" (ranks =
+    ``numpy.random.default_rng(seed).permutation(n)``), "input" (``arange(n)``) or an int32 [n]
+    tensor of distinct ranks.  Points with a non-finite coordinate are dropped.  The walk runs as
+    parallel rounds (``aarmvs_cloud_thin``, ``rounds_per_call`` per call) whose fixpoint IS the
+    sequential result; the round count does not depend on ``rounds_per_call``.  The host reads the
+    number of undecided points back after each call."""
+    radius = float(np.float32(radius))
+    if not (math.isfinite(radius) and radius > 0.0):
+        raise ValueError("aarmvs: radius must be finite and > 0")
+    rounds_per_call = int(rounds_per_call)
+    if rounds_per_call < 1:
+        raise ValueError("aarmvs: rounds_per_call must be >= 1")
+    if isinstance(xyz, torch.Tensor) and xyz.dim() == 2:
+        rank = _ranks(order, seed, xyz.shape[0])
+    xyz = _cloud(xyz, "xyz")
+    n, dev = xyz.shape[0], xyz.device
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), 0
+    lo, hi = _bounds([xyz])
+    cell = max(radius, float((hi - lo).max()) / (AXIS_CELLS - 2))
+    s_xyz, s_keys, perm = _sorted_by_key(xyz, lo, cell)
+    state, rounds = thin_sorted(s_xyz, s_keys, rank.to(dev)[perm].contiguous(), lo, cell, radius, rounds_per_call)
+    return torch.sort(perm[state == 1]).values, rounds
+
+
+def thin_sorted(s_xyz, s_keys, s_rank, origin, cell, radius, rounds_per_call=8, log=None):
+    """``aarmvs_cloud_thin`` on a key-sorted cloud until nothing is undecided: (state uint8 [n] in the
+    sorted layout, 1 kept / 2 removed; the number of rounds to the fixpoint).  ``log``: a list that
+    receives per call (rounds run, undecided points left, device milliseconds of the call)."""
+    n, dev = s_xyz.shape[0], s_xyz.device
+    state =[torch.empty(n, dtype=torch.uint8, device=dev) for _ in range(2)]
+    remaining = torch.empty(2, dtype=torch.int64, device=dev)
+    scratch = torch.empty(max(1, lib().aarmvs_cloud_thin_scratch_bytes(n)), dtype=torch.uint8, device=dev)
+    a = _lib.CloudThinArgs()
+    a.xyz, a.keys, a.rank, a.n = s_xyz.data_ptr(), s_keys.data_ptr(), s_rank.data_ptr(), n
+    a.origin[0], a.origin[1], a.origin[2] = (float(v) for v in origin)
+    a.cell, a.r = float(cell), float(radius)
+    a.state[0], a.state[1] = state[0].data_ptr(), state[1].data_ptr()
+    a.remaining, a.scratch = remaining.data_ptr(), scratch.data_ptr()
+    a.init, a.which = 1, 0
+    rounds = launched = 0
+    with torch.cuda.device(dev):
+        while True:
+            if launched >= n:
+                raise AarmvsError(f"aarmvs: thinning did not reach its fixpoint in n = {n} rounds")
+            k = min(rounds_per_call, n - launched)
+            if log is not None:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+            check(lib().aarmvs_cloud_thin(ctypes.byref(a), k, _stream()), "cloud_thin")
+            if log is not None:
+                e1.record()
+            launched += k
+            a.init, a.which = 0, (a.which + k) & 1
+            left, used = remaining.cpu().tolist()      # the one wait for the device per call
+            rounds += used
+            if log is not None:
+                log.append((k, left, e0.elapsed_time(e1)))
+            if left == 0:
+                break
+    return state[a.which], rounds
+
+
+_thin_points = thin   # evaluate_dtu's ``thin`` parameter is the radius
+
+
+def regions(xyz, obs_mask=None, bb=None, res=None, patch=60.0, plane=None):
+    """uint8 [n] flags of a CUDA float32 [n,3] cloud (``aarmvs_cloud_regions``): ``IN_BOX`` (1) inside
+    ``bb`` [2,3] widened by ``patch`` below and ``2 * patch`` above, ``IN_OBS`` (2) in the box and on a
+    set voxel of ``obs_mask`` (uint8 [nx,ny,nz], voxel = rint((p - bb[0]) / res)), ``ABOVE`` (4)
+    on the positive side of ``plane`` [4].  A bit whose input is None is 0; points with a non-finite
+    coordinate get 0."""
+    xyz = _cloud(xyz, "xyz")
+    n, dev = xyz.shape[0], xyz.device
+    if obs_mask is not None and (bb is None or res is None):
+        raise ValueError("aarmvs: obs_mask needs bb and res")
+    mask = dims = None
+    if obs_mask is not None:
+        mask = torch.as_tensor(obs_mask)
+        if mask.dim() != 3:
+            raise ValueError("aarmvs: obs_mask must be [nx,ny,nz]")
+        mask = (mask != 0).to(device=dev, dtype=torch.uint8).contiguous()
+        dims = (ctypes.c_int * 3)(*mask.shape)
+    bbv = None if bb is None else (ctypes.c_double * 6)(*np.asarray(bb, np.float64).reshape(6).tolist())
+    pv = None if plane is None else (ctypes.c_double * 4)(*np.asarray(plane, np.float64).reshape(4).tolist())
+    flags = torch.empty(n, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().aarmvs_cloud_regions(xyz.data_ptr(), n, None if mask is None else mask.data_ptr(), dims, bbv,
+                                         1.0 if res is None else float(res), float(patch), pv, flags.data_ptr(),
+                                         _stream()), "cloud_regions")
+    return flags
+
+
+def _load(path, names):
+    if str(path).endswith(".npz"):
+        with np.load(path) as f:
+            return {k: f[k] for k in names}
+    try:
+        from scipy.io import loadmat
+    except ImportError as e:
+        raise ImportError("aarmvs: reading a .mat file needs scipy (scipy.io.loadmat); convert the file to "
+                          ".npz with the same field names to do without it") from e
+    f = loadmat(path)
+    return {k: f[k] for k in names}
+
+
+def read_dtu_mask(path):
+    """DTU's ``ObsMask/ObsMaskN_10.mat`` (or an .npz with the same fields ``ObsMask``, ``BB``, ``Res``):
+    a dict of ``obs_mask`` uint8 [nx,ny,nz] C-contiguous (0/1), ``bb`` float64 [2,3], ``res`` float."""
+    f = _load(path, ("ObsMask", "BB", "Res"))
+    m = np.asarray(f["ObsMask"])
+    if m.ndim != 3:
+        raise ValueError(f"read_dtu_mask: ObsMask of {path} is not 3-D")
+    return dict(obs_mask=np.ascontiguousarray(m != 0).astype(np.uint8),
+                bb=np.ascontiguousarray(np.asarray(f["BB"], np.float64).reshape(2, 3)),
+                res=float(np.asarray(f["Res"], np.float64).reshape(-1)[0]))
+
+
+def read_dtu_plane(path):
+    """DTU's ``ObsMask/PlaneN.mat`` (or an .npz with the field ``P``): the plane as float64 [4]."""
+    return np.ascontiguousarray(np.asarray(_load(path, ("P",))["P"], np.float64).reshape(4))
+
+
+def _nn_in_order(query, target, origin, cell, max_dist):
+    """Distances of ``nn_sorted`` in the order of ``query`` with those == max_dist set to +inf: the
+    protocol's truncation is strict."""
+    t_sorted, t_keys, _ = _sorted_by_key(target, origin, cell)
+    q_sorted, _, q_perm = _sorted_by_key(query, origin, cell)
+    d_s, _ = nn_sorted(q_sorted, t_sorted, t_keys, None, origin, cell, max_dist, want_index=False)
+    dist = torch.empty_like(d_s)
+    dist[q_perm] = d_s
+    return torch.where(dist >= max_dist, torch.full_like(dist, float("inf")), dist)
+
+
+def evaluate_dtu(recon, gt, obs_mask, bb, res, plane, thin=0.2, patch=60.0, max_dist=20.0, seed=0, order="random"):
+    """The DTU evaluation protocol (include/aarmvs.h, "DTU protocol") of a reconstructed cloud
+    against a scan's ground truth (CUDA float32 [n,3] each) with the scan's observation mask
+    (``obs_mask``, ``bb``, ``res``: ``read_dtu_mask``) and ground plane (``read_dtu_plane``):
+      1. ``recon`` is thinned at radius ``thin`` (``thin(recon, thin, order, seed)``);
+      2. ``n_in_box`` / ``n_in_obs`` of the thinned points are IN_BOX / IN_OBS;
+      3. accuracy: from every IN_OBS point the distance to ``gt``; mean and median over the distances
+         strictly below ``max_dist``;
+      4. completeness: from every ABOVE point of ``gt`` the distance to the IN_BOX points; the same;
+      5. ``overall`` = the mean of the two means.
+    The means are ``aarmvs_cloud_stats``' fixed-order sums over the counts in the caller's point
+    order, the medians the lower middle value.  Restates the published MATLAB evaluation as its
+    common Python port does; parity with the MATLAB code itself is not pinned."""
+    recon, gt = _cloud(recon, "recon"), _cloud(gt, "gt")
+    kept, rounds = _thin_points(recon, thin, order, seed)
+    down = recon[kept]
+    flags = regions(down, obs_mask, bb, res, patch)
+    data_in, data_in_obs = down[(flags & IN_BOX) != 0], down[(flags & IN_OBS) != 0]
+    gt_above = gt[(regions(gt, plane=plane) & ABOVE) != 0]
+    out = dict(n_recon=int(recon.shape[0]), n_thinned=int(down.shape[0]), n_in_box=int(data_in.shape[0]),
+               n_in_obs=int(data_in_obs.shape[0]), n_gt=int(gt.shape[0]), n_gt_above=int(gt_above.shape[0]),
+               thin_rounds=int(rounds))
+    md, origin, cell = _checked_grid(data_in, gt, max_dist)
+    for name, which, query, target in (("accuracy", "recon", data_in_obs, gt), ("completeness", "gt", gt_above, data_in)):
+        dist = _nn_in_order(query, target, origin, cell, md)
+        st = distance_stats(dist)
+        out[name + "_mean"] = st[1] / st[0] if st[0] else float("nan")
+        out[name + "_median"] = _median(dist)
+        out[which + "_beyond_max_dist"] = int(dist.shape[0] - st[2] - st[0])
+    out["overall"] = 0.5 * (out["accuracy_mean"] + out["completeness_mean"])
+    out["recon_nonfinite"] = int((~torch.isfinite(recon).all(1)).sum())
+    out["gt_nonfinite"] = int((~torch.isfinite(gt).all(1)).sum())
+    out.update(thin=float(np.float32(thin)), patch=float(patch), max_dist=float(max_dist), seed=int(seed),
+               order=order if isinstance(order, str) else "ranks")
+    return out
+
+
+# ---------------------------------------------------------------------------------
 # PLY reader (numpy only): what aarmvs.fusion.write_ply writes, and plain ascii / binary x y z
 # ---------------------------------------------------------------------------------
 _PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2",
@@ -304,24 +504,43 @@ def build_parser():
     import argparse
     p = argparse.ArgumentParser(prog="python -m aarmvs.cloud_eval",
                                 description="Accuracy, completeness and F-score of a reconstructed cloud against "
-                                            "a ground-truth cloud (plain figures, not the official DTU / Tanks "
-                                            "and Temples protocols)")
+                                            "a ground-truth cloud: plain figures, or with --protocol dtu the DTU "
+                                            "protocol (not Tanks and Temples' alignment and cropping)")
     p.add_argument("--recon", required=True, help="the reconstructed cloud (PLY)")
     p.add_argument("--gt", required=True, help="the ground-truth cloud (PLY)")
-    p.add_argument("--max_dist", type=float, required=True, help="distances are truncated here")
+    p.add_argument("--max_dist", type=float, default=None,
+                   help="distances are truncated here (required; with --protocol dtu: default 20)")
     p.add_argument("--tau", type=float, nargs="*", default=[], help="F-score thresholds (<= max_dist)")
     p.add_argument("--voxel", type=float, default=None, help="down-sample the reconstruction to this voxel size")
     p.add_argument("--json", default=None, help="also write the result here")
     p.add_argument("--device", default="cuda")
+    p.add_argument("--protocol", choices=["dtu"], default=None,
+                   help="dtu: the DTU protocol (thinning, observation mask, plane cut) instead of the plain figures")
+    p.add_argument("--obs_mask", default=None, help="dtu: ObsMask/ObsMaskN_10.mat (or .npz: ObsMask, BB, Res)")
+    p.add_argument("--plane", default=None, help="dtu: ObsMask/PlaneN.mat (or .npz: P)")
+    p.add_argument("--thin", type=float, default=0.2, help="dtu: the thinning radius")
+    p.add_argument("--patch", type=float, default=60.0, help="dtu: the margin around the mask's box")
+    p.add_argument("--seed", type=int, default=0, help="dtu: the seed of the thinning order")
     return p
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.protocol is None and args.max_dist is None:
+        parser.error("the following arguments are required: --max_dist")
+    if args.protocol == "dtu" and (args.obs_mask is None or args.plane is None):
+        parser.error("--protocol dtu needs --obs_mask and --plane")
     dev = torch.device(args.device)
     recon = torch.from_numpy(read_ply(args.recon)["xyz"]).to(dev)
     gt = torch.from_numpy(read_ply(args.gt)["xyz"]).to(dev)
-    res = evaluate(recon, gt, args.max_dist, args.tau, args.voxel)
+    if args.protocol == "dtu":
+        m = read_dtu_mask(args.obs_mask)
+        res = evaluate_dtu(recon, gt, m["obs_mask"], m["bb"], m["res"], read_dtu_plane(args.plane), thin=args.thin,
+                           patch=args.patch, max_dist=20.0 if args.max_dist is None else args.max_dist,
+                           seed=args.seed)
+    else:
+        res = evaluate(recon, gt, args.max_dist, args.tau, args.voxel)
     print(json.dumps(res))
     if args.json:
         with open(args.json, "w") as f:

@@ -179,6 +179,13 @@ size_t cloud_voxel_workspace_bytes(long long n);
 hipError_t launch_cloud_voxel_centroids(const float* xyz, const long long* keys, long long n, float* out,
                                         long long capacity, long long* count, void* workspace,
                                         hipStream_t s);
+// the DTU protocol's thinning rounds and region flags (cloud.hip); thin with n == 0 still writes
+// remaining, regions with n == 0 launches nothing
+size_t cloud_thin_scratch_bytes(long long n);
+hipError_t launch_cloud_thin(const aarmvs_cloud_thin_args* a, int rounds, hipStream_t s);
+hipError_t launch_cloud_regions(const float* xyz, long long n, const unsigned char* mask, const int* dims,
+                                const double* bb, double res, double patch, const double* plane,
+                                unsigned char* flags, hipStream_t s);
 // xmax (optional, to_nhwc only): atomic max of |in| as float bits
 hipError_t launch_layout(const float* in, float* out, int B, int C, int HW, bool to_nhwc,
                          hipStream_t s, unsigned* xmax = nullptr);

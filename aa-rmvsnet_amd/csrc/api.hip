@@ -1570,4 +1570,70 @@ int aarmvs_cloud_voxel_centroids(const float* sorted_xyz, const long long* sorte
   return e == hipSuccess ? AARMVS_OK : hip_fail(e, "cloud_voxel_centroids");
 }
 
+size_t aarmvs_cloud_thin_scratch_bytes(long long n) {
+  return cloud_count_ok(n) ? cloud_thin_scratch_bytes(n) : 0;
+}
+
+int aarmvs_cloud_thin(const aarmvs_cloud_thin_args* a, int rounds, hipStream_t stream) {
+  if (!a) return fail(AARMVS_ERR_INVALID, "cloud_thin: null args");
+  if (!cloud_count_ok(a->n)) return fail(AARMVS_ERR_INVALID, "cloud_thin: need 0 <= n < 2^31");
+  if (rounds < 1) return fail(AARMVS_ERR_INVALID, "cloud_thin: need rounds >= 1");
+  if (a->which != 0 && a->which != 1) return fail(AARMVS_ERR_INVALID, "cloud_thin: which must be 0 or 1");
+  if (!a->remaining || !a->scratch ||
+      (a->n > 0 && (!a->xyz || !a->keys || !a->rank || !a->state[0] || !a->state[1])))
+    return fail(AARMVS_ERR_INVALID, "cloud_thin: null pointer argument");
+  if (!std::isfinite(a->origin[0]) || !std::isfinite(a->origin[1]) || !std::isfinite(a->origin[2]))
+    return fail(AARMVS_ERR_INVALID, "cloud_thin: origin must be finite");
+  if (!cloud_cell_ok(a->cell)) return fail(AARMVS_ERR_INVALID, "cloud_thin: cell must be finite and > 0");
+  if (!(a->r >= 0.0f) || std::isinf(a->r)) return fail(AARMVS_ERR_INVALID, "cloud_thin: r must be finite and >= 0");
+  if (a->cell < (double)a->r) return fail(AARMVS_ERR_INVALID, "cloud_thin: cell must be >= r");
+  // a round's threads read the inputs and one state while others write the other state; the
+  // per-block values and `remaining` are written between the rounds' reads
+  const size_t n = (size_t)a->n, scr = cloud_thin_scratch_bytes(a->n);
+  const void* outs[4] = {a->state[0], a->state[1], a->remaining, a->scratch};
+  const size_t out_bytes[4] = {n, n, 2 * sizeof(long long), scr};
+  const void* ins[3] = {a->xyz, a->keys, a->rank};
+  const size_t in_bytes[3] = {12 * n, 8 * n, 4 * n};
+  for (int o = 0; o < 4; ++o) {
+    if (out_bytes[o] == 0) continue;
+    for (int i = 0; i < 3; ++i)
+      if (in_bytes[i] > 0 && ranges_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i]))
+        return fail(AARMVS_ERR_INVALID, "cloud_thin: an output must not alias an input");
+    for (int p = o + 1; p < 4; ++p)
+      if (out_bytes[p] > 0 && ranges_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p]))
+        return fail(AARMVS_ERR_INVALID, "cloud_thin: the outputs must not alias each other");
+  }
+  hipError_t e = launch_cloud_thin(a, rounds, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "cloud_thin");
+}
+
+int aarmvs_cloud_regions(const float* xyz, long long n, const unsigned char* mask, const int* dims,
+                         const double* bb, double res, double patch, const double* plane,
+                         unsigned char* flags_out, hipStream_t stream) {
+  if (!cloud_count_ok(n)) return fail(AARMVS_ERR_INVALID, "cloud_regions: need 0 <= n < 2^31");
+  if ((n > 0 && (!xyz || !flags_out)) || (mask && (!bb || !dims)))
+    return fail(AARMVS_ERR_INVALID, "cloud_regions: null pointer argument");
+  if (bb)
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(bb[k])) return fail(AARMVS_ERR_INVALID, "cloud_regions: bb must be finite");
+  if (!(patch >= 0.0) || std::isinf(patch))
+    return fail(AARMVS_ERR_INVALID, "cloud_regions: patch must be finite and >= 0");
+  size_t voxels = 0;
+  if (mask) {
+    if (!(res > 0.0) || std::isinf(res)) return fail(AARMVS_ERR_INVALID, "cloud_regions: res must be finite and > 0");
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1)
+      return fail(AARMVS_ERR_INVALID, "cloud_regions: every mask dimension must be >= 1");
+    voxels = 1;
+    for (int k = 0; k < 3; ++k) {
+      voxels *= (size_t)dims[k];                      // each factor < 2^31: no overflow before the test
+      if (voxels >= ((size_t)1 << 31)) return fail(AARMVS_ERR_INVALID, "cloud_regions: the mask has 2^31 voxels or more");
+    }
+  }
+  if (n > 0 && (ranges_overlap(flags_out, (size_t)n, xyz, 12 * (size_t)n) ||
+                (mask && ranges_overlap(flags_out, (size_t)n, mask, voxels))))
+    return fail(AARMVS_ERR_INVALID, "cloud_regions: flags_out must not alias an input");
+  hipError_t e = launch_cloud_regions(xyz, n, mask, dims, bb, res, patch, plane, flags_out, stream);
+  return e == hipSuccess ? AARMVS_OK : hip_fail(e, "cloud_regions");
+}
+
 }  // extern "C"

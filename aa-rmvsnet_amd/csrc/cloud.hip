@@ -1,6 +1,7 @@
 // Point-cloud evaluation for gfx950 (include/aarmvs.h, "Point-cloud evaluation"): the grid keys of
 // a cloud, the truncated exact nearest neighbour of every query point in a key-sorted target cloud,
-// the fixed-order statistics of the distances, and the per-voxel centroids of a key-sorted cloud.
+// the fixed-order statistics of the distances, the per-voxel centroids of a key-sorted cloud, and
+// the DTU protocol's greedy thinning (in parallel rounds) and region flags.
 // All arithmetic is float64 with every operation rounded on its own (built with -ffp-contract=off;
 // the __d*_rn forms say so where the definition names an order).  No atomics anywhere: every
 // result is the same on every run.
@@ -350,6 +351,174 @@ voxel_write_kernel(const float* __restrict__ xyz, const long long* __restrict__ 
   }
 }
 
+// ---------------------------------------------------------------------------------
+// Greedy thinning in parallel rounds (include/aarmvs.h, "DTU protocol"): one thread per point of
+// the key-sorted cloud.  A decided point copies its state byte through and is done, which is what
+// carries the later rounds (a byte read and a byte written per point).  An undecided point walks
+// the rows of its box as cloud_nn_kernel does and tests per candidate the cheap things first: the
+// rank (4 B), the state byte, then d2 (12 B).  A round reads st_in only and writes st_out only.
+// Per block, as plain stores: the number of its points still undecided after the round, and the
+// last round of this call at whose start the block held an undecided point.
+// ---------------------------------------------------------------------------------
+constexpr unsigned char kUndecided = 0, kKept = 1, kRemoved = 2;
+constexpr long long kAxisMask = (1LL << AARMVS_CLOUD_AXIS_BITS) - 1;
+
+__global__ void __launch_bounds__(kCloudThreads)
+thin_init_kernel(const long long* __restrict__ keys, long long n, unsigned char* __restrict__ st) {
+  const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
+  if (i < n) st[i] = keys[i] == kNoKey ? kRemoved : kUndecided;
+}
+
+struct ThinArgs {
+  const float* xyz;
+  const long long* keys;
+  const int* rank;
+  long long n;
+  Grid g;
+  double reach;   // r (1 + 2^-40)
+  double r2;      // (double) r * (double) r
+  const unsigned char* st_in;
+  unsigned char* st_out;
+  int* block_cnt;
+  int* block_last;
+  int round;      // 1-based within the call
+};
+
+// the new state of undecided point i (in the grid: its key holds its cell)
+__device__ __forceinline__ unsigned char thin_decide(const ThinArgs& a, long long i) {
+  const float* pp = a.xyz + (size_t)i * 3;
+  const double p[3] = {(double)pp[0], (double)pp[1], (double)pp[2]};
+  const long long key = a.keys[i];
+  const int c[3] = {(int)(key & kAxisMask), (int)((key >> 21) & kAxisMask), (int)(key >> 42)};
+  const int my = a.rank[i];
+  int lo[3], hi[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double tl = cell_quotient(__dsub_rn(p[k], a.reach), a.g.o[k], a.g.cell);
+    const double th = cell_quotient(__dadd_rn(p[k], a.reach), a.g.o[k], a.g.cell);
+    lo[k] = (int)fmin(fmax(tl, 0.0), (double)c[k]);
+    hi[k] = (int)fmax(fmin(th, kAxisCells - 1.0), (double)c[k]);
+  }
+  bool waits = false;   // an undecided lower-ranked neighbour was seen
+  for (int iz = lo[2]; iz <= hi[2]; ++iz) {
+    for (int iy = lo[1]; iy <= hi[1]; ++iy) {
+      const long long base = ((long long)iz << 42) | ((long long)iy << 21);
+      const long long last = base | (long long)hi[0];
+      for (long long j = lower_bound(a.keys, a.n, base | (long long)lo[0]); j < a.n && a.keys[j] <= last; ++j) {
+        if (a.rank[j] >= my) continue;   // (the point itself included)
+        const unsigned char s = a.st_in[j];
+        if (s == kRemoved || (s == kUndecided && waits)) continue;
+        const float* t = a.xyz + (size_t)j * 3;
+        const double dx = p[0] - (double)t[0], dy = p[1] - (double)t[1], dz = p[2] - (double)t[2];
+        const double d2 = __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
+        if (!(d2 <= a.r2)) continue;
+        if (s == kKept) return kRemoved;
+        waits = true;
+      }
+    }
+  }
+  return waits ? kUndecided : kKept;
+}
+
+__global__ void __launch_bounds__(kCloudThreads) thin_round_kernel(ThinArgs a) {
+  const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
+  unsigned char before = kRemoved, after = kRemoved;
+  if (i < a.n) {
+    before = after = a.st_in[i];
+    if (before == kUndecided) after = thin_decide(a, i);
+    a.st_out[i] = after;
+  }
+  const int active = __syncthreads_or(before == kUndecided);
+  const int left = __syncthreads_count(after == kUndecided);
+  if (threadIdx.x == 0) {
+    a.block_cnt[blockIdx.x] = left;
+    if (a.round == 1 || active) a.block_last[blockIdx.x] = active ? a.round : 0;
+  }
+}
+
+// out[0] = the sum of block_cnt, out[1] = the maximum of block_last, over nblk blocks (integers: any
+// order gives the same bits; the order is fixed all the same)
+__global__ void __launch_bounds__(kCloudThreads)
+thin_reduce_kernel(const int* __restrict__ block_cnt, const int* __restrict__ block_last, int nblk,
+                   long long* __restrict__ out) {
+  __shared__ long long wsum[kCloudThreads / 64];
+  __shared__ int wmax[kCloudThreads / 64];
+  long long s = 0;
+  int m = 0;
+  for (int i = threadIdx.x; i < nblk; i += kCloudThreads) {
+    s += block_cnt[i];
+    m = max(m, block_last[i]);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    s += __shfl_xor(s, o, 64);
+    m = max(m, __shfl_xor(m, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    wsum[threadIdx.x >> 6] = s;
+    wmax[threadIdx.x >> 6] = m;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < kCloudThreads / 64; ++w) {
+      s += wsum[w];
+      m = max(m, wmax[w]);
+    }
+    out[0] = s;
+    out[1] = m;
+  }
+}
+
+// ---------------------------------------------------------------------------------
+// Region flags of a cloud (include/aarmvs.h, "Region tests"): one thread per point.
+// ---------------------------------------------------------------------------------
+struct RegionArgs {
+  double lo[3], hi[3];   // BB[0] - patch, BB[1] + 2 patch
+  double bb0[3];
+  double res;
+  double plane[4];
+  int dims[3];
+  int has_box, has_plane;
+  const unsigned char* mask;
+};
+
+__global__ void __launch_bounds__(kCloudThreads)
+cloud_regions_kernel(const float* __restrict__ xyz, long long n, RegionArgs a, unsigned char* __restrict__ flags) {
+  const long long i = (long long)blockIdx.x * kCloudThreads + threadIdx.x;
+  if (i >= n) return;
+  const float* pp = xyz + (size_t)i * 3;
+  const double p[3] = {(double)pp[0], (double)pp[1], (double)pp[2]};
+  const double inf = __longlong_as_double(0x7ff0000000000000LL);
+  unsigned char f = 0;
+  if (fabs(p[0]) < inf && fabs(p[1]) < inf && fabs(p[2]) < inf) {
+    if (a.has_box) {
+      bool in_box = true;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) in_box = in_box && p[k] >= a.lo[k] && p[k] < a.hi[k];
+      if (in_box) {
+        f |= 1;
+        if (a.mask) {
+          long long g[3];
+          bool in = true;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            const double t = rint(__ddiv_rn(__dsub_rn(p[k], a.bb0[k]), a.res));
+            in = in && t >= 0.0 && t < (double)a.dims[k];
+            g[k] = in ? (long long)t : 0;
+          }
+          if (in && a.mask[(g[0] * a.dims[1] + g[1]) * a.dims[2] + g[2]] != 0) f |= 2;
+        }
+      }
+    }
+    if (a.has_plane) {
+      const double s = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(a.plane[0], p[0]), __dmul_rn(a.plane[1], p[1])),
+                                           __dmul_rn(a.plane[2], p[2])), a.plane[3]);
+      if (s > 0.0) f |= 4;
+    }
+  }
+  flags[i] = f;
+}
+
 int blocks_of(long long n, int chunk) { return (int)((n + chunk - 1) / chunk); }
 
 Grid make_grid(const double* origin, double cell) {
@@ -431,6 +600,71 @@ hipError_t launch_cloud_voxel_centroids(const float* xyz, const long long* keys,
   if ((e = hipGetLastError()) != hipSuccess || nb == 0) return e;
   hipLaunchKernelGGL(voxel_write_kernel, dim3(nb), dim3(kCloudThreads), 0, s, xyz, keys, n, blk, out,
                      capacity);
+  return hipGetLastError();
+}
+
+// two ints per block of kCloudThreads points: the undecided count and the last active round
+size_t cloud_thin_scratch_bytes(long long n) {
+  return ((size_t)std::max(1, blocks_of(n, kCloudThreads)) * 2 * sizeof(int) + 255) / 256 * 256;
+}
+
+hipError_t launch_cloud_thin(const aarmvs_cloud_thin_args* in, int rounds, hipStream_t s) {
+  const int nb = blocks_of(in->n, kCloudThreads);
+  int* block_cnt = static_cast<int*>(in->scratch);
+  int* block_last = block_cnt + std::max(1, nb);
+  ProfScope ps(s, K_FUSION_POINTS);
+  hipError_t e = hipSuccess;
+  if (nb > 0) {
+    if (in->init) {
+      hipLaunchKernelGGL(thin_init_kernel, dim3(nb), dim3(kCloudThreads), 0, s, in->keys, in->n,
+                         in->state[in->which]);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    ThinArgs a{};
+    a.xyz = in->xyz;
+    a.keys = in->keys;
+    a.rank = in->rank;
+    a.n = in->n;
+    a.g = make_grid(in->origin, in->cell);
+    const double r = (double)in->r;
+    a.reach = r * (1.0 + 0x1p-40);
+    a.r2 = r * r;
+    a.block_cnt = block_cnt;
+    a.block_last = block_last;
+    for (int k = 1; k <= rounds; ++k) {
+      a.st_in = in->state[(in->which + k - 1) & 1];
+      a.st_out = in->state[(in->which + k) & 1];
+      a.round = k;
+      hipLaunchKernelGGL(thin_round_kernel, dim3(nb), dim3(kCloudThreads), 0, s, a);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+  }
+  hipLaunchKernelGGL(thin_reduce_kernel, dim3(1), dim3(kCloudThreads), 0, s, block_cnt, block_last, nb,
+                     in->remaining);
+  return hipGetLastError();
+}
+
+hipError_t launch_cloud_regions(const float* xyz, long long n, const unsigned char* mask, const int* dims,
+                                const double* bb, double res, double patch, const double* plane,
+                                unsigned char* flags, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  RegionArgs a{};
+  a.has_box = bb != nullptr;
+  a.has_plane = plane != nullptr;
+  a.mask = mask;
+  a.res = mask ? res : 1.0;
+  for (int k = 0; k < 3; ++k) {
+    if (bb) {
+      a.bb0[k] = bb[k];
+      a.lo[k] = bb[k] - patch;
+      a.hi[k] = bb[3 + k] + 2.0 * patch;
+    }
+    a.dims[k] = mask ? dims[k] : 1;
+  }
+  for (int k = 0; k < 4; ++k) a.plane[k] = plane ? plane[k] : 0.0;
+  ProfScope ps(s, K_FUSION_POINTS);
+  hipLaunchKernelGGL(cloud_regions_kernel, dim3(blocks_of(n, kCloudThreads)), dim3(kCloudThreads), 0, s, xyz, n, a,
+                     flags);
   return hipGetLastError();
 }
 

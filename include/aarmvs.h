@@ -682,10 +682,11 @@ int aarmvs_fusion_points_normals(const aarmvs_fusion_points_args* args, const fl
 /* ---------------------------------------------------------------------------
  * Point-cloud evaluation (not in the reference): the one operation under the DTU accuracy /
  * completeness figures and the Tanks and Temples precision / recall / F-score -- for every point
- * of cloud A the distance to its nearest point of cloud B -- and what goes with it.  The official
- * protocols (DTU's observation masks, ground-plane cut and reducePts; Tanks and Temples' alignment
- * and cropping) need dataset files and are NOT implemented; aarmvs/cloud_eval.py computes the plain
- * figures.
+ * of cloud A the distance to its nearest point of cloud B -- and what goes with it.  The DTU
+ * protocol's steps (reducePts, the observation mask, the ground-plane cut) are defined under "DTU
+ * protocol" below; Tanks and Temples' alignment and cropping need dataset files and are NOT
+ * implemented.  aarmvs/cloud_eval.py computes the plain figures (evaluate) and the DTU ones
+ * (evaluate_dtu).
  *
  * Definition.  A cloud is float32 [n,3] device memory.  A GRID is (origin[3] float64, cell float64
  * > 0).  All arithmetic is float64, every operation rounded on its own (no fused multiply-add).
@@ -769,6 +770,84 @@ size_t aarmvs_cloud_voxel_workspace_bytes(long long n);
 int aarmvs_cloud_voxel_centroids(const float* sorted_xyz, const long long* sorted_keys, long long n,
                                  float* out_xyz, long long capacity, long long* count, void* workspace,
                                  hipStream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * DTU protocol (not in the reference): the steps of the published DTU evaluation that the plain
+ * figures leave out -- reducePts (a greedy thinning), the observation mask and the ground-plane
+ * cut.  Same rules as above: float64, every operation rounded on its own, d2 = (dx dx + dy dy) +
+ * dz dz on exact float32 -> float64 differences, the caller's stream, no wait, no allocation, no
+ * atomics, bit-identical run to run, timed under "fusion_points".
+ *
+ * Thinning.  Inputs: a cloud, a radius r > 0 (float32, promoted to float64) and a RANK per point
+ *   (int32, all different).  Points that are not in the grid (a non-finite coordinate included) are
+ *   dropped: never kept, nobody's neighbour.  Two in-grid points are NEIGHBOURS when d2 <=
+ *   (double)r (double)r -- inclusive, so a point exactly at r is a neighbour, and so are coincident
+ *   points.  KEPT is what the sequential walk in ascending rank keeps: a point is kept iff no
+ *   lower-ranked neighbour is kept.  That set is the lexicographically first maximal independent
+ *   set of the neighbour graph under the rank order, and the unique fixpoint of the
+ * Round rule.  State per point: 0 undecided, 1 kept, 2 removed.  A round reads state_in and writes
+ *   state_out for EVERY point (ping-pong between two buffers, decided points are copied through).
+ *   For an undecided point p, over its neighbours q with rank(q) < rank(p):
+ *     any q kept -> p removed;  else any q undecided -> p stays undecided;  else -> p kept.
+ *   A round never reads what the same round writes, so the number of rounds to the fixpoint is
+ *   part of the definition and the same on every run.  Every round decides at least the
+ *   lowest-ranked undecided point: n rounds is a hard upper bound (reached by a line of points in
+ *   rank order), with random ranks the count stays logarithmic.
+ * aarmvs_cloud_thin runs `rounds` >= 1 rounds on a KEY-SORTED cloud (`xyz`, `keys`, `rank` in the
+ *   same sorted layout; the grid's cell must be >= r).  The current state is in state[which]; round
+ *   k = 1 .. rounds reads state[(which + k - 1) & 1] and writes state[(which + k) & 1], so the call
+ *   LEAVES THE STATE IN state[(which + rounds) & 1].  init != 0 (a first call) first sets
+ *   state[which] from the keys: INT64_MAX -> removed, else undecided.  `remaining` receives two
+ *   int64: [0] the number of still-undecided points after the last round, [1] the number of this
+ *   call's rounds that began with an undecided point (0 .. rounds; summed over the calls it is the
+ *   number of rounds to the fixpoint whatever `rounds` per call was).  Both come from per-block
+ *   values written as plain stores into `scratch` (aarmvs_cloud_thin_scratch_bytes(n) bytes) and
+ *   one block that adds them in a fixed order.  One thread per point; an undecided point walks the
+ *   (i_y, i_z) rows of the box [cell(p_a - reach), cell(p_a + reach)], reach = r (1 + 2^-40), one
+ *   lower_bound per row as aarmvs_cloud_nn does (the cell function is monotone, so the box holds
+ *   every neighbour; cell >= r keeps it at 3 cells per axis, 9 rows, one more where p +- reach
+ *   crosses a further face), and stops at the first kept lower-ranked neighbour.
+ *   AARMVS_ERR_INVALID, before any launch: NULL args or a NULL required pointer; n < 0 or >= 2^31;
+ *   origin or cell not finite, cell <= 0; r negative or not finite; cell < r; rounds < 1; which not
+ *   0 or 1; an output (the two states, remaining, scratch) overlapping an input or another output.
+ *   n == 0: a successful no-op that writes remaining = {0, 0}.
+ * Region tests.  Observation mask M: uint8 [nx,ny,nz], C-contiguous in that index order; BB float64
+ *   [2][3]; Res float64 > 0; patch float64 >= 0.  For a point p with finite coordinates:
+ *     IN_BOX  when for every axis a: p_a >= BB[0][a] - patch and p_a < BB[1][a] + 2 patch;
+ *     g_a = rint((p_a - BB[0][a]) / Res), round-half-to-even;
+ *     IN_OBS  when IN_BOX, 0 <= g_a < n_a on every axis and M[g_x,g_y,g_z] != 0;
+ *     ABOVE   when ((P0 x + P1 y) + P2 z) + P3 > 0 for the plane P [4] float64.
+ *   A point with a non-finite coordinate is in no region.
+ * aarmvs_cloud_regions: flags_out[i] = IN_BOX | IN_OBS << 1 | ABOVE << 2 of xyz[i]; one thread per
+ *   point.  `dims` [3], `bb` [2][3] and `plane` [4] are HOST arrays, `mask` is device memory.  A bit
+ *   whose input is NULL is 0: bb NULL -> bits 0 and 1, mask NULL -> bit 1, plane NULL -> bit 2
+ *   (mask needs bb and dims).  AARMVS_ERR_INVALID: n < 0 or >= 2^31; NULL xyz or flags_out with n >
+ *   0; mask without bb or dims; bb not finite; patch negative or not finite; with a mask: Res not
+ *   finite or <= 0, a dimension < 1, 2^31 voxels or more; flags_out overlapping xyz or the mask.
+ *   n == 0: a successful no-op.
+ * The protocol itself (thin the reconstruction, accuracy from its IN_OBS points to the ground
+ * truth, completeness from the ABOVE ground-truth points to its IN_BOX points, distances strictly
+ * below max_dist) is aarmvs/cloud_eval.py's evaluate_dtu.
+ * ------------------------------------------------------------------------- */
+typedef struct aarmvs_cloud_thin_args {
+  const float* xyz;               /* [n,3] device, sorted by key                            */
+  const long long* keys;          /* [n] device, ascending, INT64_MAX entries last          */
+  const int* rank;                /* [n] device, in the sorted layout, all different        */
+  long long n;                    /* 0 <= n < 2^31                                          */
+  double origin[3];               /* the grid: finite                                       */
+  double cell;                    /* finite, > 0, >= r                                      */
+  float r;                        /* finite, >= 0                                           */
+  int init;                       /* != 0: set state[which] from the keys first             */
+  int which;                      /* 0 or 1: the buffer that holds the current state        */
+  unsigned char* state[2];        /* [n] device each                                        */
+  long long* remaining;           /* [2] device out                                         */
+  void* scratch;                  /* aarmvs_cloud_thin_scratch_bytes(n) bytes, device       */
+} aarmvs_cloud_thin_args;
+size_t aarmvs_cloud_thin_scratch_bytes(long long n);
+int aarmvs_cloud_thin(const aarmvs_cloud_thin_args* args, int rounds, hipStream_t stream);
+int aarmvs_cloud_regions(const float* xyz, long long n, const unsigned char* mask, const int* dims,
+                         const double* bb, double res, double patch, const double* plane,
+                         unsigned char* flags_out, hipStream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Epilogue of the evidential head (evidential/models.py:385-459): from the three
