@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <string>
 
 #include "../../include/aarmvs.h"
 #include "sweep_schedule.h"
@@ -133,11 +134,6 @@ struct SweepGeom {
 };
 
 hipError_t launch_pack_params(const float* raw, float* packed, hipStream_t s);
-hipError_t launch_homo_warp(const float* src, const float* rel, const float* depth, int B, int C,
-                            int H, int W, float* out, hipStream_t s);
-size_t homo_warp_bwd_workspace_bytes(int B, int C, int H, int W);
-hipError_t launch_homo_warp_bwd(const float* gout, const float* rel, const float* depth, int B, int C, int H,
-                                int W, float* gsrc, void* workspace, hipStream_t s);
 
 struct CostArgs {
   const float* ref;
@@ -151,41 +147,7 @@ struct CostArgs {
 // statistics of every plane (omega conv + omega_stats<1> + <2>); cost_x_group then writes
 // each plane's cost slice to x0 + k ws.x_plane (and, for plane omega_k, the omega weights
 // to omega_out).  Both use the t1 / statistics slots of the workspace: one group at a time.
-// NCHW <-> NHWC copy of a [B][C][HW] / [B][HW][C] fp32 tensor (API edges only)
-// depth-map fusion core (fusion.hip)
-hipError_t launch_fusion_filter(const aarmvs_fusion_args* a, hipStream_t s);
-// the same with the visibility de-duplication (d is not NULL)
-hipError_t launch_fusion_filter_dedup(const aarmvs_fusion_args* a, const aarmvs_fusion_dedup_args* d,
-                                      hipStream_t s);
-// one cv2.pyrDown level of an interleaved float32 image, and the ordered world points of a
-// reference view's kept pixels (fusion.hip)
-hipError_t launch_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t s);
-size_t fusion_points_workspace_bytes(int H, int W);
-// (normal_map != nullptr: the kept pixels' normals go to nxyz as well)
-hipError_t launch_fusion_points(const aarmvs_fusion_points_args* a, const float* normal_map, float* nxyz,
-                                hipStream_t s);
-// per-pixel normals of a view's averaged depth map (fusion.hip)
-hipError_t launch_fusion_normals(const aarmvs_fusion_normals_args* a, hipStream_t s);
-// point-cloud evaluation (cloud.hip): grid keys, the truncated nearest neighbour in a key-sorted
-// target, the distances' statistics (thresholds: a host array of nthr values) and the voxel
-// centroids of a key-sorted cloud; n == 0 / nq == 0 launch nothing (the statistics write zeros)
-hipError_t launch_cloud_keys(const float* xyz, long long n, const double* origin, double cell,
-                             long long* keys, hipStream_t s);
-hipError_t launch_cloud_nn(const aarmvs_cloud_nn_args* a, hipStream_t s);
-size_t cloud_stats_scratch_bytes(long long n);
-hipError_t launch_cloud_stats(const float* dist, long long n, const float* thresholds, int nthr, double* out,
-                              void* scratch, hipStream_t s);
-size_t cloud_voxel_workspace_bytes(long long n);
-hipError_t launch_cloud_voxel_centroids(const float* xyz, const long long* keys, long long n, float* out,
-                                        long long capacity, long long* count, void* workspace,
-                                        hipStream_t s);
-// the DTU protocol's thinning rounds and region flags (cloud.hip); thin with n == 0 still writes
-// remaining, regions with n == 0 launches nothing
-size_t cloud_thin_scratch_bytes(long long n);
-hipError_t launch_cloud_thin(const aarmvs_cloud_thin_args* a, int rounds, hipStream_t s);
-hipError_t launch_cloud_regions(const float* xyz, long long n, const unsigned char* mask, const int* dims,
-                                const double* bb, double res, double patch, const double* plane,
-                                unsigned char* flags, hipStream_t s);
+// launch_layout: NCHW <-> NHWC copy of a [B][C][HW] / [B][HW][C] fp32 tensor (API edges only);
 // xmax (optional, to_nhwc only): atomic max of |in| as float bits
 hipError_t launch_layout(const float* in, float* out, int B, int C, int HW, bool to_nhwc,
                          hipStream_t s, unsigned* xmax = nullptr);
@@ -248,87 +210,32 @@ hipError_t launch_head_wta(const float* params, const SweepGeom& g, const UnetIO
 // ^ refine_state: the sub-plane refinement's per-pixel state (16 B per pixel) or null; non-null
 // launches the refining instantiation of the head kernel.  posterior_state: likewise the
 // depth-posterior statistics' state (16 B per pixel), independent of the former
-hipError_t launch_wta_update(const float* cost, const float* depth_d, float* max_prob,
-                             float* depth, float* exp_sum, int B, int HW, hipStream_t s);
 hipError_t launch_finalize(const SweepGeom& g, const Workspace& ws, float* depth_out,
                            float* conf_out, hipStream_t s);
-hipError_t launch_softmax_depth(const float* cost, float* prob, int B, int D, int HW,
-                                hipStream_t s);
-// sub-plane refinement of the WTA: the outputs after n planes from the WTA images and the state,
-// one plane's standalone update (d == 0 resets the state), and the whole from a cost volume
+// the sweep's opt-in outputs after n planes, from the WTA images and the per-pixel state: the
+// sub-plane refinement, and the depth-posterior statistics (mean, std, entropy, runner-up)
 hipError_t launch_refine_finalize(const float* max_prob, const float* exp_sum, const float* depth,
                                   const void* state, const float* depth_values, int B, int D, int n,
                                   int HW, float* depth_refined, float* conf_window, int* index,
                                   hipStream_t s);
-hipError_t launch_wta_refine_update(const float* cost, const float* depth_d, int d, float* max_prob,
-                                    float* depth, float* exp_sum, void* state, int B, int HW,
-                                    hipStream_t s);
-hipError_t launch_refine_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
-                                   float* depth_refined, float* conf_window, int* index,
-                                   hipStream_t s);
-// depth-posterior statistics of the WTA (mean, std, entropy, runner-up): the outputs from exp_sum
-// and the state, one plane's standalone update (d == 0 resets the state), the whole from a volume
 hipError_t launch_posterior_finalize(const float* exp_sum, const void* state, int B, int HW,
                                      float* mean, float* sd, float* entropy, float* runner_up,
                                      hipStream_t s);
-hipError_t launch_wta_posterior_update(const float* cost, const float* depth_d, int d, float* max_prob,
-                                       float* depth, float* exp_sum, void* state, int B, int HW,
-                                       hipStream_t s);
-hipError_t launch_posterior_from_cost(const float* cost, const float* depth_values, int B, int D,
-                                      int HW, float* mean, float* sd, float* entropy,
-                                      float* runner_up, hipStream_t s);
-// the evidential head's epilogue (evidential.hip): forward when g_head is null (ev [4][HW],
-// pc [D][HW]), else the backward from g_ev / g_pc (either may be null) into g_head
-hipError_t launch_evidential(const float* const head[3], const float* dv, int D, int HW, float* ev,
-                             float* pc, const float* g_ev, const float* g_pc, float* const g_head[3],
-                             hipStream_t s);
-// the sampling half of FeatNet's deformable conv (deform.hip): val from x (forward), or dL/dx,
-// dL/d offset, dL/d m from dL/d val (backward)
-struct DfArgs {
-  const float* x;        // [B][H][W][C]
-  const float* off;      // [B][18][h][w]
-  const float* m;        // [B][9][h][w] or null (no modulation)
-  int B, H, W, h, w, stride, pad;
-  float* val;            // [B][h w][9][C]
-  const float* gval;     // backward: dL/d val
-  float* gx;             // backward: dL/d x, NHWC, accumulated
-  float* goff;           // backward: dL/d offset
-  float* gm;             // backward: dL/d m (null if m is null)
-};
-hipError_t launch_deform_sample(const DfArgs& a, bool bwd, hipStream_t s);
-// GroupNorm of NCHW [B][C][HW] fp32 (group_norm.hip): mean_rstd [B][G][2]; gamma / beta may
-// be null (1 / 0); scratch of gn_scratch_bytes(B, C, HW); bwd also writes s1 = sum dy xhat and
-// s2 = sum dy per (b, c) (the per-sample dgamma / dbeta terms)
-size_t gn_scratch_bytes(int B, int C, int HW);
-hipError_t launch_group_norm_fwd(const float* x, const float* gamma, const float* beta, int B,
-                                 int C, int HW, int G, float eps, float* y, float* mean_rstd,
-                                 void* scratch, hipStream_t s);
-// ConvLSTMCell gate math (lstm_train.hip): z [B][4 hid][HW] -> h, c [B][hid][HW]; backward
-// from dh, dc (either may be null: zero) to dz and dc_prev
-hipError_t launch_lstm_gates_fwd(const float* z, const float* c_prev, int B, int hid, int HW,
-                                 float* h, float* c, hipStream_t s);
-hipError_t launch_lstm_gates_bwd(const float* z, const float* c_prev, const float* dh,
-                                 const float* dc, int B, int hid, int HW, float* dz, float* dc_prev,
-                                 hipStream_t s);
-hipError_t launch_group_norm_bwd(const float* dy, const float* x, const float* gamma,
-                                 const float* mean_rstd, int B, int C, int HW, int G, float* dx,
-                                 float* s1, float* s2, void* scratch, hipStream_t s);
-// The classification loss from the cost volume and the masked depth metrics (cls_loss.hip).
-// Their scratch holds [B][cls_loss_blocks(HW)][kClsPartials] fp64 per-block partials (the loss
-// uses two of the slots, the metrics 2 + the thresholds); lse is [2][B][HW] (an fp32 pair).
-constexpr int kClsPartials = 2 + AARMVS_MAX_THRESHOLDS;
-int cls_loss_blocks(int HW);
-hipError_t launch_cls_loss_fwd(const float* cost, const float* depth_gt, const float* mask,
-                               const float* dvals, int B, int D, int HW, float* loss,
-                               float* wta_depth, float* max_prob, float* lse, int* gt, float* coef,
-                               void* scratch, hipStream_t s);
-hipError_t launch_cls_loss_bwd(const float* cost, const float* lse, const int* gt, const float* mask,
-                               const float* coef, const float* g, int B, int D, int HW,
-                               float* grad_cost, hipStream_t s);
-// thresholds: a host array of nthr values
-hipError_t launch_depth_metrics(const float* est, const float* gt, const float* mask, int B, int HW,
-                                const float* thresholds, int nthr, double* out, void* scratch,
-                                hipStream_t s);
+
+// ---------------------------------------------------------------------------
+// The ABI boundary's shared pieces.  The thread's error string lives in api.hip alone
+// (aarmvs_last_error reads it): every unit's entry points report through these.
+// ---------------------------------------------------------------------------
+int fail(int code, const std::string& msg);
+int hip_fail(hipError_t e, const char* where);
+int check_geom(int B, int H, int W, int nsrc);
+// the tail of an entry point that makes one launch
+inline int launched(hipError_t e, const char* who) { return e == hipSuccess ? AARMVS_OK : hip_fail(e, who); }
+// [p, p + n) and [q, q + m) share a byte
+inline bool ranges_overlap(const void* p, size_t n, const void* q, size_t m) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + m && b < a + n;
+}
 
 int cu_count();
 

@@ -531,8 +531,8 @@ Grid make_grid(const double* origin, double cell) {
 }  // namespace
 
 // (all of these are timed under the points' profile id: the list of kernel names is fixed)
-hipError_t launch_cloud_keys(const float* xyz, long long n, const double* origin, double cell,
-                             long long* keys, hipStream_t s) {
+static hipError_t launch_cloud_keys(const float* xyz, long long n, const double* origin, double cell,
+                                    long long* keys, hipStream_t s) {
   if (n == 0) return hipSuccess;
   ProfScope ps(s, K_FUSION_POINTS);
   hipLaunchKernelGGL(cloud_keys_kernel, dim3(blocks_of(n, kCloudThreads)), dim3(kCloudThreads), 0, s, xyz, n,
@@ -540,7 +540,7 @@ hipError_t launch_cloud_keys(const float* xyz, long long n, const double* origin
   return hipGetLastError();
 }
 
-hipError_t launch_cloud_nn(const aarmvs_cloud_nn_args* in, hipStream_t s) {
+static hipError_t launch_cloud_nn(const aarmvs_cloud_nn_args* in, hipStream_t s) {
   if (in->nq == 0) return hipSuccess;
   NnArgs a{};
   a.query = in->query;
@@ -561,12 +561,12 @@ hipError_t launch_cloud_nn(const aarmvs_cloud_nn_args* in, hipStream_t s) {
   return hipGetLastError();
 }
 
-size_t cloud_stats_scratch_bytes(long long n) {
+static size_t cloud_stats_scratch_bytes(long long n) {
   return ((size_t)std::max(1, blocks_of(n, kStatChunk)) * kStatVals * sizeof(double) + 255) / 256 * 256;
 }
 
-hipError_t launch_cloud_stats(const float* dist, long long n, const float* thresholds, int nthr, double* out,
-                              void* scratch, hipStream_t s) {
+static hipError_t launch_cloud_stats(const float* dist, long long n, const float* thresholds, int nthr, double* out,
+                                     void* scratch, hipStream_t s) {
   const int nblk = blocks_of(n, kStatChunk);
   double* part = static_cast<double*>(scratch);
   CloudThresholds thr{};
@@ -581,13 +581,13 @@ hipError_t launch_cloud_stats(const float* dist, long long n, const float* thres
   return hipGetLastError();
 }
 
-size_t cloud_voxel_workspace_bytes(long long n) {
+static size_t cloud_voxel_workspace_bytes(long long n) {
   return ((size_t)std::max(1, blocks_of(n, kVoxChunk)) * sizeof(int) + 255) / 256 * 256;
 }
 
-hipError_t launch_cloud_voxel_centroids(const float* xyz, const long long* keys, long long n, float* out,
-                                        long long capacity, long long* count, void* workspace,
-                                        hipStream_t s) {
+static hipError_t launch_cloud_voxel_centroids(const float* xyz, const long long* keys, long long n, float* out,
+                                               long long capacity, long long* count, void* workspace,
+                                               hipStream_t s) {
   int* blk = static_cast<int*>(workspace);
   const int nb = blocks_of(n, kVoxChunk);
   ProfScope ps(s, K_FUSION_POINTS);
@@ -604,11 +604,11 @@ hipError_t launch_cloud_voxel_centroids(const float* xyz, const long long* keys,
 }
 
 // two ints per block of kCloudThreads points: the undecided count and the last active round
-size_t cloud_thin_scratch_bytes(long long n) {
+static size_t cloud_thin_scratch_bytes(long long n) {
   return ((size_t)std::max(1, blocks_of(n, kCloudThreads)) * 2 * sizeof(int) + 255) / 256 * 256;
 }
 
-hipError_t launch_cloud_thin(const aarmvs_cloud_thin_args* in, int rounds, hipStream_t s) {
+static hipError_t launch_cloud_thin(const aarmvs_cloud_thin_args* in, int rounds, hipStream_t s) {
   const int nb = blocks_of(in->n, kCloudThreads);
   int* block_cnt = static_cast<int*>(in->scratch);
   int* block_last = block_cnt + std::max(1, nb);
@@ -644,9 +644,9 @@ hipError_t launch_cloud_thin(const aarmvs_cloud_thin_args* in, int rounds, hipSt
   return hipGetLastError();
 }
 
-hipError_t launch_cloud_regions(const float* xyz, long long n, const unsigned char* mask, const int* dims,
-                                const double* bb, double res, double patch, const double* plane,
-                                unsigned char* flags, hipStream_t s) {
+static hipError_t launch_cloud_regions(const float* xyz, long long n, const unsigned char* mask, const int* dims,
+                                       const double* bb, double res, double patch, const double* plane,
+                                       unsigned char* flags, hipStream_t s) {
   if (n == 0) return hipSuccess;
   RegionArgs a{};
   a.has_box = bb != nullptr;
@@ -669,3 +669,162 @@ hipError_t launch_cloud_regions(const float* xyz, long long n, const unsigned ch
 }
 
 }  // namespace aarmvs
+
+using namespace aarmvs;
+
+extern "C" {
+
+static bool cloud_count_ok(long long n) { return n >= 0 && n < (1LL << 31); }
+static bool cloud_cell_ok(double cell) { return std::isfinite(cell) && cell > 0.0; }
+static bool cloud_origin_ok(const double* o) {
+  return std::isfinite(o[0]) && std::isfinite(o[1]) && std::isfinite(o[2]);
+}
+
+int aarmvs_cloud_keys(const float* xyz, long long n, const double* origin, double cell, long long* keys_out,
+                      hipStream_t stream) {
+  if (!cloud_count_ok(n)) return fail(AARMVS_ERR_INVALID, "cloud_keys: need 0 <= n < 2^31");
+  if (!origin || (n > 0 && (!xyz || !keys_out)))
+    return fail(AARMVS_ERR_INVALID, "cloud_keys: null pointer argument");
+  if (!cloud_origin_ok(origin)) return fail(AARMVS_ERR_INVALID, "cloud_keys: origin must be finite");
+  if (!cloud_cell_ok(cell)) return fail(AARMVS_ERR_INVALID, "cloud_keys: cell must be finite and > 0");
+  if (n > 0 && ranges_overlap(keys_out, 8 * (size_t)n, xyz, 12 * (size_t)n))
+    return fail(AARMVS_ERR_INVALID, "cloud_keys: keys_out must not alias xyz");
+  return launched(launch_cloud_keys(xyz, n, origin, cell, keys_out, stream), "cloud_keys");
+}
+
+int aarmvs_cloud_nn(const aarmvs_cloud_nn_args* a, hipStream_t stream) {
+  if (!a) return fail(AARMVS_ERR_INVALID, "cloud_nn: null args");
+  if (!cloud_count_ok(a->nq) || !cloud_count_ok(a->m))
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: need 0 <= nq, m < 2^31");
+  if ((a->nq > 0 && (!a->query || !a->dist_out)) || (a->m > 0 && (!a->target || !a->target_keys)))
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: null pointer argument");
+  if (!cloud_origin_ok(a->origin)) return fail(AARMVS_ERR_INVALID, "cloud_nn: origin must be finite");
+  if (!cloud_cell_ok(a->cell)) return fail(AARMVS_ERR_INVALID, "cloud_nn: cell must be finite and > 0");
+  if (!(a->max_dist >= 0.0f) || std::isinf(a->max_dist))
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: max_dist must be finite and >= 0");
+  if ((double)a->max_dist / a->cell > (double)AARMVS_CLOUD_MAX_RINGS)
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: max_dist / cell exceeds AARMVS_CLOUD_MAX_RINGS");
+  // other threads still read the inputs while a thread writes its outputs
+  const size_t nq = (size_t)a->nq, m = (size_t)a->m;
+  const void* outs[2] = {a->dist_out, a->index_out};
+  for (int o = 0; o < 2; ++o) {
+    if (!outs[o] || nq == 0) continue;
+    if (ranges_overlap(outs[o], 4 * nq, a->query, 12 * nq) ||
+        (m > 0 && (ranges_overlap(outs[o], 4 * nq, a->target, 12 * m) ||
+                   ranges_overlap(outs[o], 4 * nq, a->target_keys, 8 * m) ||
+                   (a->target_ids && ranges_overlap(outs[o], 4 * nq, a->target_ids, 4 * m)))))
+      return fail(AARMVS_ERR_INVALID, o == 0 ? "cloud_nn: dist_out must not alias an input"
+                                             : "cloud_nn: index_out must not alias an input");
+  }
+  if (nq > 0 && a->index_out && ranges_overlap(a->dist_out, 4 * nq, a->index_out, 4 * nq))
+    return fail(AARMVS_ERR_INVALID, "cloud_nn: dist_out and index_out must not alias");
+  return launched(launch_cloud_nn(a, stream), "cloud_nn");
+}
+
+size_t aarmvs_cloud_stats_scratch_bytes(long long n) {
+  return cloud_count_ok(n) ? cloud_stats_scratch_bytes(n) : 0;
+}
+
+int aarmvs_cloud_stats(const float* dist, long long n, const float* thresholds, int n_thresholds, double* out,
+                       void* scratch, hipStream_t stream) {
+  if (!cloud_count_ok(n)) return fail(AARMVS_ERR_INVALID, "cloud_stats: need 0 <= n < 2^31");
+  if (n_thresholds < 0 || n_thresholds > AARMVS_MAX_THRESHOLDS)
+    return fail(AARMVS_ERR_INVALID, "cloud_stats: at most 8 thresholds");
+  if (!out || !scratch || (n > 0 && !dist) || (n_thresholds > 0 && !thresholds))
+    return fail(AARMVS_ERR_INVALID, "cloud_stats: null pointer argument");
+  // blocks still read dist while others write their partials, and the reduce writes out after
+  const size_t out_bytes = (3 + (size_t)n_thresholds) * sizeof(double), scr = cloud_stats_scratch_bytes(n);
+  if (n > 0 && (ranges_overlap(out, out_bytes, dist, 4 * (size_t)n) || ranges_overlap(scratch, scr, dist, 4 * (size_t)n)))
+    return fail(AARMVS_ERR_INVALID, "cloud_stats: out and scratch must not alias dist");
+  if (ranges_overlap(out, out_bytes, scratch, scr))
+    return fail(AARMVS_ERR_INVALID, "cloud_stats: out must not alias scratch");
+  return launched(launch_cloud_stats(dist, n, thresholds, n_thresholds, out, scratch, stream), "cloud_stats");
+}
+
+size_t aarmvs_cloud_voxel_workspace_bytes(long long n) {
+  return cloud_count_ok(n) ? cloud_voxel_workspace_bytes(n) : 0;
+}
+
+int aarmvs_cloud_voxel_centroids(const float* sorted_xyz, const long long* sorted_keys, long long n,
+                                 float* out_xyz, long long capacity, long long* count, void* workspace,
+                                 hipStream_t stream) {
+  if (!cloud_count_ok(n)) return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: need 0 <= n < 2^31");
+  if (capacity < 0) return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: negative capacity");
+  if (!count || !workspace || (n > 0 && (!sorted_xyz || !sorted_keys)))
+    return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: null pointer argument");
+  if (capacity > 0 && !out_xyz)
+    return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: null out_xyz with capacity > 0");
+  if (n > 0 && capacity > 0 &&
+      (ranges_overlap(out_xyz, 12 * (size_t)capacity, sorted_xyz, 12 * (size_t)n) ||
+       ranges_overlap(out_xyz, 12 * (size_t)capacity, sorted_keys, 8 * (size_t)n)))
+    return fail(AARMVS_ERR_INVALID, "cloud_voxel_centroids: out_xyz must not alias an input");
+  return launched(launch_cloud_voxel_centroids(sorted_xyz, sorted_keys, n, out_xyz, capacity, count, workspace,
+                                               stream),
+                  "cloud_voxel_centroids");
+}
+
+size_t aarmvs_cloud_thin_scratch_bytes(long long n) {
+  return cloud_count_ok(n) ? cloud_thin_scratch_bytes(n) : 0;
+}
+
+int aarmvs_cloud_thin(const aarmvs_cloud_thin_args* a, int rounds, hipStream_t stream) {
+  if (!a) return fail(AARMVS_ERR_INVALID, "cloud_thin: null args");
+  if (!cloud_count_ok(a->n)) return fail(AARMVS_ERR_INVALID, "cloud_thin: need 0 <= n < 2^31");
+  if (rounds < 1) return fail(AARMVS_ERR_INVALID, "cloud_thin: need rounds >= 1");
+  if (a->which != 0 && a->which != 1) return fail(AARMVS_ERR_INVALID, "cloud_thin: which must be 0 or 1");
+  if (!a->remaining || !a->scratch ||
+      (a->n > 0 && (!a->xyz || !a->keys || !a->rank || !a->state[0] || !a->state[1])))
+    return fail(AARMVS_ERR_INVALID, "cloud_thin: null pointer argument");
+  if (!cloud_origin_ok(a->origin)) return fail(AARMVS_ERR_INVALID, "cloud_thin: origin must be finite");
+  if (!cloud_cell_ok(a->cell)) return fail(AARMVS_ERR_INVALID, "cloud_thin: cell must be finite and > 0");
+  if (!(a->r >= 0.0f) || std::isinf(a->r)) return fail(AARMVS_ERR_INVALID, "cloud_thin: r must be finite and >= 0");
+  if (a->cell < (double)a->r) return fail(AARMVS_ERR_INVALID, "cloud_thin: cell must be >= r");
+  // a round's threads read the inputs and one state while others write the other state; the
+  // per-block values and `remaining` are written between the rounds' reads
+  const size_t n = (size_t)a->n, scr = cloud_thin_scratch_bytes(a->n);
+  const void* outs[4] = {a->state[0], a->state[1], a->remaining, a->scratch};
+  const size_t out_bytes[4] = {n, n, 2 * sizeof(long long), scr};
+  const void* ins[3] = {a->xyz, a->keys, a->rank};
+  const size_t in_bytes[3] = {12 * n, 8 * n, 4 * n};
+  for (int o = 0; o < 4; ++o) {
+    if (out_bytes[o] == 0) continue;
+    for (int i = 0; i < 3; ++i)
+      if (in_bytes[i] > 0 && ranges_overlap(outs[o], out_bytes[o], ins[i], in_bytes[i]))
+        return fail(AARMVS_ERR_INVALID, "cloud_thin: an output must not alias an input");
+    for (int p = o + 1; p < 4; ++p)
+      if (out_bytes[p] > 0 && ranges_overlap(outs[o], out_bytes[o], outs[p], out_bytes[p]))
+        return fail(AARMVS_ERR_INVALID, "cloud_thin: the outputs must not alias each other");
+  }
+  return launched(launch_cloud_thin(a, rounds, stream), "cloud_thin");
+}
+
+int aarmvs_cloud_regions(const float* xyz, long long n, const unsigned char* mask, const int* dims,
+                         const double* bb, double res, double patch, const double* plane,
+                         unsigned char* flags_out, hipStream_t stream) {
+  if (!cloud_count_ok(n)) return fail(AARMVS_ERR_INVALID, "cloud_regions: need 0 <= n < 2^31");
+  if ((n > 0 && (!xyz || !flags_out)) || (mask && (!bb || !dims)))
+    return fail(AARMVS_ERR_INVALID, "cloud_regions: null pointer argument");
+  if (bb)
+    for (int k = 0; k < 6; ++k)
+      if (!std::isfinite(bb[k])) return fail(AARMVS_ERR_INVALID, "cloud_regions: bb must be finite");
+  if (!(patch >= 0.0) || std::isinf(patch))
+    return fail(AARMVS_ERR_INVALID, "cloud_regions: patch must be finite and >= 0");
+  size_t voxels = 0;
+  if (mask) {
+    if (!(res > 0.0) || std::isinf(res)) return fail(AARMVS_ERR_INVALID, "cloud_regions: res must be finite and > 0");
+    if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1)
+      return fail(AARMVS_ERR_INVALID, "cloud_regions: every mask dimension must be >= 1");
+    voxels = 1;
+    for (int k = 0; k < 3; ++k) {
+      voxels *= (size_t)dims[k];                      // each factor < 2^31: no overflow before the test
+      if (voxels >= ((size_t)1 << 31)) return fail(AARMVS_ERR_INVALID, "cloud_regions: the mask has 2^31 voxels or more");
+    }
+  }
+  if (n > 0 && (ranges_overlap(flags_out, (size_t)n, xyz, 12 * (size_t)n) ||
+                (mask && ranges_overlap(flags_out, (size_t)n, mask, voxels))))
+    return fail(AARMVS_ERR_INVALID, "cloud_regions: flags_out must not alias an input");
+  return launched(launch_cloud_regions(xyz, n, mask, dims, bb, res, patch, plane, flags_out, stream),
+                  "cloud_regions");
+}
+
+}  // extern "C"

@@ -13,6 +13,10 @@
 
 namespace aarmvs {
 
+// The scratch holds [B][cls_loss_blocks(HW)][kClsPartials] fp64 per-block partials (the loss
+// uses two of the slots, the metrics 2 + the thresholds); lse is [2][B][HW] (an fp32 pair).
+constexpr int kClsPartials = 2 + AARMVS_MAX_THRESHOLDS;
+
 namespace {
 
 constexpr int kThreads = 256;
@@ -243,12 +247,12 @@ depth_metrics_reduce_kernel(const double* __restrict__ part, int B, int nblk, in
 
 }  // namespace
 
-int cls_loss_blocks(int HW) { return (HW + kThreads - 1) / kThreads; }
+static int cls_loss_blocks(int HW) { return (HW + kThreads - 1) / kThreads; }
 
-hipError_t launch_cls_loss_fwd(const float* cost, const float* depth_gt, const float* mask,
-                               const float* dvals, int B, int D, int HW, float* loss,
-                               float* wta_depth, float* max_prob, float* lse, int* gt, float* coef,
-                               void* scratch, hipStream_t s) {
+static hipError_t launch_cls_loss_fwd(const float* cost, const float* depth_gt, const float* mask,
+                                      const float* dvals, int B, int D, int HW, float* loss,
+                                      float* wta_depth, float* max_prob, float* lse, int* gt, float* coef,
+                                      void* scratch, hipStream_t s) {
   const int nblk = cls_loss_blocks(HW);
   double* part = static_cast<double*>(scratch);
   {
@@ -263,18 +267,18 @@ hipError_t launch_cls_loss_fwd(const float* cost, const float* depth_gt, const f
   return hipGetLastError();
 }
 
-hipError_t launch_cls_loss_bwd(const float* cost, const float* lse, const int* gt, const float* mask,
-                               const float* coef, const float* g, int B, int D, int HW,
-                               float* grad_cost, hipStream_t s) {
+static hipError_t launch_cls_loss_bwd(const float* cost, const float* lse, const int* gt, const float* mask,
+                                      const float* coef, const float* g, int B, int D, int HW,
+                                      float* grad_cost, hipStream_t s) {
   ProfScope ps(s, K_CLS_LOSS_BWD);
   hipLaunchKernelGGL(cls_loss_bwd_kernel, dim3(cls_loss_blocks(HW), B), dim3(kThreads), 0, s, cost,
                      lse, gt, mask, coef, g, D, HW, grad_cost);
   return hipGetLastError();
 }
 
-hipError_t launch_depth_metrics(const float* est, const float* gt, const float* mask, int B, int HW,
-                                const float* thresholds, int nthr, double* out, void* scratch,
-                                hipStream_t s) {
+static hipError_t launch_depth_metrics(const float* est, const float* gt, const float* mask, int B, int HW,
+                                       const float* thresholds, int nthr, double* out, void* scratch,
+                                       hipStream_t s) {
   const int nblk = cls_loss_blocks(HW);
   double* part = static_cast<double*>(scratch);
   Thresholds thr{};
@@ -290,3 +294,60 @@ hipError_t launch_depth_metrics(const float* est, const float* gt, const float* 
 }
 
 }  // namespace aarmvs
+
+using namespace aarmvs;
+
+extern "C" {
+
+// B rides in gridDim.y; the pixel index of a block's last thread must fit an int
+static int cls_check(const char* who, int B, int HW) {
+  if (B < 1 || HW < 1) return fail(AARMVS_ERR_INVALID, std::string(who) + ": need B, HW >= 1");
+  if (B > 65535 || HW > 0x7fffffff - 256)
+    return fail(AARMVS_ERR_INVALID, std::string(who) + ": need B <= 65535 and HW < 2^31 - 256");
+  return AARMVS_OK;
+}
+
+size_t aarmvs_cls_loss_scratch_bytes(int B, int HW) {
+  if (cls_check("cls_loss_scratch_bytes", B, HW)) return 0;
+  return (size_t)B * cls_loss_blocks(HW) * kClsPartials * sizeof(double);
+}
+
+int aarmvs_cls_loss(const float* cost, const float* depth_gt, const float* mask,
+                    const float* depth_values, int B, int D, int HW, float* loss, float* wta_depth,
+                    float* max_prob, float* lse, int* gt_index, float* coef, void* scratch,
+                    hipStream_t stream) {
+  if (!cost || !depth_gt || !mask || !depth_values || !loss || !wta_depth || !lse || !gt_index ||
+      !coef || !scratch)
+    return fail(AARMVS_ERR_INVALID, "cls_loss: null pointer argument");
+  if (int rc = cls_check("cls_loss", B, HW)) return rc;
+  if (D < 1) return fail(AARMVS_ERR_INVALID, "cls_loss: need D >= 1");
+  return launched(launch_cls_loss_fwd(cost, depth_gt, mask, depth_values, B, D, HW, loss, wta_depth,
+                                      max_prob, lse, gt_index, coef, scratch, stream),
+                  "cls_loss");
+}
+
+int aarmvs_cls_loss_backward(const float* cost, const float* lse, const int* gt_index,
+                             const float* mask, const float* coef, const float* grad_loss, int B,
+                             int D, int HW, float* grad_cost, hipStream_t stream) {
+  if (!cost || !lse || !gt_index || !mask || !coef || !grad_loss || !grad_cost)
+    return fail(AARMVS_ERR_INVALID, "cls_loss_backward: null pointer argument");
+  if (int rc = cls_check("cls_loss_backward", B, HW)) return rc;
+  if (D < 1) return fail(AARMVS_ERR_INVALID, "cls_loss_backward: need D >= 1");
+  return launched(launch_cls_loss_bwd(cost, lse, gt_index, mask, coef, grad_loss, B, D, HW, grad_cost, stream),
+                  "cls_loss_backward");
+}
+
+int aarmvs_depth_metrics(const float* depth_est, const float* depth_gt, const float* mask, int B,
+                         int HW, const float* thresholds, int n_thresholds, double* out,
+                         void* scratch, hipStream_t stream) {
+  if (!depth_est || !depth_gt || !mask || !out || !scratch || (n_thresholds > 0 && !thresholds))
+    return fail(AARMVS_ERR_INVALID, "depth_metrics: null pointer argument");
+  if (int rc = cls_check("depth_metrics", B, HW)) return rc;
+  if (n_thresholds < 0 || n_thresholds > AARMVS_MAX_THRESHOLDS)
+    return fail(AARMVS_ERR_INVALID, "depth_metrics: at most 8 thresholds");
+  return launched(launch_depth_metrics(depth_est, depth_gt, mask, B, HW, thresholds, n_thresholds, out,
+                                       scratch, stream),
+                  "depth_metrics");
+}
+
+}  // extern "C"

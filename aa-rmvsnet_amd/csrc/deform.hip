@@ -28,6 +28,18 @@ namespace aarmvs {
 constexpr int kDfC = 32;   // channels (FeatNet's deformable convs are 32 -> 32)
 constexpr int kDfTaps = 9;
 
+// val from x (forward), or dL/dx, dL/d offset, dL/d m from dL/d val (backward)
+struct DfArgs {
+  const float* x;        // [B][H][W][C]
+  const float* off;      // [B][18][h][w]
+  const float* m;        // [B][9][h][w] or null (no modulation)
+  int B, H, W, h, w, stride, pad;
+  float* val;            // [B][h w][9][C]
+  const float* gval;     // backward: dL/d val
+  float* gx;             // backward: dL/d x, NHWC, accumulated
+  float* goff;           // backward: dL/d offset
+  float* gm;             // backward: dL/d m (null if m is null)
+};
 
 struct DfPos {
   float prc, pcc;              // clamped sampling point
@@ -141,7 +153,7 @@ __global__ void __launch_bounds__(256) deform_sample_kernel(DfArgs a) {
   }
 }
 
-hipError_t launch_deform_sample(const DfArgs& a, bool bwd, hipStream_t s) {
+static hipError_t launch_deform_sample(const DfArgs& a, bool bwd, hipStream_t s) {
   ProfScope ps(s, K_DEFORM);
   const long long items = (long long)a.B * a.h * a.w * kDfTaps;
   const long long blocks = (items + 7) / 8;
@@ -154,3 +166,61 @@ hipError_t launch_deform_sample(const DfArgs& a, bool bwd, hipStream_t s) {
 }
 
 }  // namespace aarmvs
+
+using namespace aarmvs;
+
+extern "C" {
+
+static int deform_check(const char* who, const float* x, const float* offset, int B, int C, int H,
+                        int W, int h, int w, int stride, int pad) {
+  if (!x || !offset) return fail(AARMVS_ERR_INVALID, std::string(who) + ": null pointer");
+  if (C != AARMVS_DEFORM_C)
+    return fail(AARMVS_ERR_INVALID, std::string(who) + ": C must be 32 (FeatNet's deformable convs)");
+  if (B < 1 || H < 1 || W < 1 || h < 1 || w < 1 || stride < 1 || pad < 0)
+    return fail(AARMVS_ERR_INVALID, std::string(who) + ": bad geometry");
+  return AARMVS_OK;
+}
+
+static DfArgs deform_args(const float* x, const float* offset, const float* mask, int B, int H,
+                          int W, int h, int w, int stride, int pad) {
+  DfArgs a{};
+  a.x = x;
+  a.off = offset;
+  a.m = mask;
+  a.B = B;
+  a.H = H;
+  a.W = W;
+  a.h = h;
+  a.w = w;
+  a.stride = stride;
+  a.pad = pad;
+  return a;
+}
+
+int aarmvs_deform_sample(const float* x_nhwc, const float* offset, const float* mask, int B, int C,
+                         int H, int W, int h, int w, int stride, int pad, float* val,
+                         hipStream_t stream) {
+  if (int rc = deform_check("deform_sample", x_nhwc, offset, B, C, H, W, h, w, stride, pad)) return rc;
+  if (!val) return fail(AARMVS_ERR_INVALID, "deform_sample: null pointer");
+  DfArgs a = deform_args(x_nhwc, offset, mask, B, H, W, h, w, stride, pad);
+  a.val = val;
+  return launched(launch_deform_sample(a, false, stream), "deform_sample");
+}
+
+int aarmvs_deform_sample_backward(const float* x_nhwc, const float* offset, const float* mask, int B,
+                                  int C, int H, int W, int h, int w, int stride, int pad,
+                                  const float* grad_val, float* grad_x_nhwc, float* grad_offset,
+                                  float* grad_mask, hipStream_t stream) {
+  if (int rc = deform_check("deform_sample_backward", x_nhwc, offset, B, C, H, W, h, w, stride, pad))
+    return rc;
+  if (!grad_val || !grad_x_nhwc || !grad_offset || (mask && !grad_mask))
+    return fail(AARMVS_ERR_INVALID, "deform_sample_backward: null pointer");
+  DfArgs a = deform_args(x_nhwc, offset, mask, B, H, W, h, w, stride, pad);
+  a.gval = grad_val;
+  a.gx = grad_x_nhwc;
+  a.goff = grad_offset;
+  a.gm = mask ? grad_mask : nullptr;
+  return launched(launch_deform_sample(a, true, stream), "deform_sample_backward");
+}
+
+}  // extern "C"

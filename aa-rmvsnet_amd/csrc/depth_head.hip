@@ -168,8 +168,8 @@ __global__ void __launch_bounds__(256) wta_update_kernel(const float* __restrict
   }
 }
 
-hipError_t launch_wta_update(const float* cost, const float* depth_d, float* max_prob,
-                             float* depth, float* exp_sum, int B, int HW, hipStream_t s) {
+static hipError_t launch_wta_update(const float* cost, const float* depth_d, float* max_prob,
+                                    float* depth, float* exp_sum, int B, int HW, hipStream_t s) {
   const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
   ProfScope ps(s, K_HEAD_WTA);
   hipLaunchKernelGGL(wta_update_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_d, max_prob,
@@ -537,9 +537,9 @@ hipError_t launch_refine_finalize(const float* max_prob, const float* exp_sum, c
   return hipGetLastError();
 }
 
-hipError_t launch_wta_refine_update(const float* cost, const float* depth_d, int d, float* max_prob,
-                                    float* depth, float* exp_sum, void* state, int B, int HW,
-                                    hipStream_t s) {
+static hipError_t launch_wta_refine_update(const float* cost, const float* depth_d, int d, float* max_prob,
+                                           float* depth, float* exp_sum, void* state, int B, int HW,
+                                           hipStream_t s) {
   const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
   ProfScope ps(s, K_HEAD_WTA);
   hipLaunchKernelGGL(wta_refine_update_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_d, d,
@@ -547,9 +547,9 @@ hipError_t launch_wta_refine_update(const float* cost, const float* depth_d, int
   return hipGetLastError();
 }
 
-hipError_t launch_refine_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
-                                   float* depth_refined, float* conf_window, int* index,
-                                   hipStream_t s) {
+static hipError_t launch_refine_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
+                                          float* depth_refined, float* conf_window, int* index,
+                                          hipStream_t s) {
   const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
   ProfScope ps(s, K_REFINE);
   hipLaunchKernelGGL(refine_from_cost_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_values,
@@ -567,9 +567,9 @@ hipError_t launch_posterior_finalize(const float* exp_sum, const void* state, in
   return hipGetLastError();
 }
 
-hipError_t launch_wta_posterior_update(const float* cost, const float* depth_d, int d, float* max_prob,
-                                       float* depth, float* exp_sum, void* state, int B, int HW,
-                                       hipStream_t s) {
+static hipError_t launch_wta_posterior_update(const float* cost, const float* depth_d, int d, float* max_prob,
+                                              float* depth, float* exp_sum, void* state, int B, int HW,
+                                              hipStream_t s) {
   const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
   ProfScope ps(s, K_HEAD_WTA);
   hipLaunchKernelGGL(wta_posterior_update_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_d, d,
@@ -577,9 +577,9 @@ hipError_t launch_wta_posterior_update(const float* cost, const float* depth_d, 
   return hipGetLastError();
 }
 
-hipError_t launch_posterior_from_cost(const float* cost, const float* depth_values, int B, int D,
-                                      int HW, float* mean, float* sd, float* entropy,
-                                      float* runner_up, hipStream_t s) {
+static hipError_t launch_posterior_from_cost(const float* cost, const float* depth_values, int B, int D,
+                                             int HW, float* mean, float* sd, float* entropy,
+                                             float* runner_up, hipStream_t s) {
   const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
   ProfScope ps(s, K_REFINE);
   hipLaunchKernelGGL(posterior_from_cost_kernel, dim3(blocks, B), dim3(256), 0, s, cost, depth_values,
@@ -587,8 +587,8 @@ hipError_t launch_posterior_from_cost(const float* cost, const float* depth_valu
   return hipGetLastError();
 }
 
-hipError_t launch_softmax_depth(const float* cost, float* prob, int B, int D, int HW,
-                                hipStream_t s) {
+static hipError_t launch_softmax_depth(const float* cost, float* prob, int B, int D, int HW,
+                                       hipStream_t s) {
   const int blocks = std::max(1, std::min((HW + 255) / 256, 4096));
   ProfScope ps(s, K_SOFTMAX);
   hipLaunchKernelGGL(softmax_depth_kernel, dim3(blocks, B), dim3(256), 0, s, cost, prob, D, HW);
@@ -596,3 +596,92 @@ hipError_t launch_softmax_depth(const float* cost, float* prob, int B, int D, in
 }
 
 }  // namespace aarmvs
+
+using namespace aarmvs;
+
+extern "C" {
+
+size_t aarmvs_posterior_state_bytes(int B, int HW) {
+  if (B < 1 || HW < 1) return 0;
+  return (size_t)16 * B * HW;
+}
+
+size_t aarmvs_refine_state_bytes(int B, int HW) {
+  if (B < 1 || HW < 1) return 0;
+  return (size_t)16 * B * HW;
+}
+
+int aarmvs_wta_update(const float* cost, const float* depth_d, float* max_prob, float* depth_map,
+                      float* exp_sum, int B, int HW, hipStream_t stream) {
+  if (!cost || !depth_d || !max_prob || !depth_map || !exp_sum || B < 1 || HW < 1)
+    return fail(AARMVS_ERR_INVALID, "wta_update: bad arguments");
+  return launched(launch_wta_update(cost, depth_d, max_prob, depth_map, exp_sum, B, HW, stream), "wta_update");
+}
+
+int aarmvs_wta_refine_update(const float* cost, int d, float* max_prob, float* depth_map,
+                             float* exp_sum, void* state, const float* depth_d, int B, int HW,
+                             hipStream_t stream) {
+  if (!cost || !depth_d || !max_prob || !depth_map || !exp_sum || !state || B < 1 || HW < 1 || d < 0)
+    return fail(AARMVS_ERR_INVALID, "wta_refine_update: bad arguments");
+  return launched(launch_wta_refine_update(cost, depth_d, d, max_prob, depth_map, exp_sum, state, B, HW, stream),
+                  "wta_refine_update");
+}
+
+int aarmvs_wta_refine_finalize(const float* max_prob, const float* depth_map, const float* exp_sum,
+                               const void* state, const float* depth_values, int B, int D, int n,
+                               int HW, float* depth_refined, float* conf_window, int* index,
+                               hipStream_t stream) {
+  if (!max_prob || !depth_map || !exp_sum || !state || !depth_values)
+    return fail(AARMVS_ERR_INVALID, "wta_refine_finalize: null pointer argument");
+  if (B < 1 || HW < 1 || D < 1 || n < 1 || n > D)
+    return fail(AARMVS_ERR_INVALID, "wta_refine_finalize: need B, HW >= 1 and 1 <= n <= D");
+  return launched(launch_refine_finalize(max_prob, exp_sum, depth_map, state, depth_values, B, D, n, HW,
+                                         depth_refined, conf_window, index, stream),
+                  "wta_refine_finalize");
+}
+
+int aarmvs_refine_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
+                            float* depth_refined, float* conf_window, int* index, hipStream_t stream) {
+  if (!cost || !depth_values)
+    return fail(AARMVS_ERR_INVALID, "refine_from_cost: null pointer argument");
+  if (B < 1 || D < 1 || HW < 1)
+    return fail(AARMVS_ERR_INVALID, "refine_from_cost: need B, D, HW >= 1");
+  return launched(launch_refine_from_cost(cost, depth_values, B, D, HW, depth_refined, conf_window, index, stream),
+                  "refine_from_cost");
+}
+
+int aarmvs_wta_posterior_update(const float* cost, int d, float* max_prob, float* depth_map,
+                                float* exp_sum, void* state, const float* depth_d, int B, int HW,
+                                hipStream_t stream) {
+  if (!cost || !depth_d || !max_prob || !depth_map || !exp_sum || !state || B < 1 || HW < 1 || d < 0)
+    return fail(AARMVS_ERR_INVALID, "wta_posterior_update: bad arguments");
+  return launched(launch_wta_posterior_update(cost, depth_d, d, max_prob, depth_map, exp_sum, state, B, HW, stream),
+                  "wta_posterior_update");
+}
+
+int aarmvs_wta_posterior_finalize(const float* exp_sum, const void* state, int B, int HW, float* mean,
+                                  float* std_out, float* entropy, float* runner_up, hipStream_t stream) {
+  if (!exp_sum || !state) return fail(AARMVS_ERR_INVALID, "wta_posterior_finalize: null pointer argument");
+  if (B < 1 || HW < 1) return fail(AARMVS_ERR_INVALID, "wta_posterior_finalize: need B, HW >= 1");
+  return launched(launch_posterior_finalize(exp_sum, state, B, HW, mean, std_out, entropy, runner_up, stream),
+                  "wta_posterior_finalize");
+}
+
+int aarmvs_posterior_from_cost(const float* cost, const float* depth_values, int B, int D, int HW,
+                               float* mean, float* std_out, float* entropy, float* runner_up,
+                               hipStream_t stream) {
+  if (!cost || !depth_values)
+    return fail(AARMVS_ERR_INVALID, "posterior_from_cost: null pointer argument");
+  if (B < 1 || D < 1 || HW < 1)
+    return fail(AARMVS_ERR_INVALID, "posterior_from_cost: need B, D, HW >= 1");
+  return launched(launch_posterior_from_cost(cost, depth_values, B, D, HW, mean, std_out, entropy, runner_up, stream),
+                  "posterior_from_cost");
+}
+
+int aarmvs_softmax_depth(const float* cost, float* prob, int B, int D, int HW, hipStream_t stream) {
+  if (!cost || !prob || B < 1 || D < 1 || HW < 1)
+    return fail(AARMVS_ERR_INVALID, "softmax_depth: bad arguments");
+  return launched(launch_softmax_depth(cost, prob, B, D, HW, stream), "softmax_depth");
+}
+
+}  // extern "C"

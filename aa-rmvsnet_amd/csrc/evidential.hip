@@ -198,9 +198,9 @@ __global__ void __launch_bounds__(256) evidential_bwd_kernel(EvArgs a) {
   }
 }
 
-hipError_t launch_evidential(const float* const head[3], const float* dv, int D, int HW, float* ev,
-                             float* pc, const float* g_ev, const float* g_pc, float* const g_head[3],
-                             hipStream_t s) {
+static hipError_t launch_evidential(const float* const head[3], const float* dv, int D, int HW, float* ev,
+                                    float* pc, const float* g_ev, const float* g_pc, float* const g_head[3],
+                                    hipStream_t s) {
   if (D != kEvD) return hipErrorInvalidValue;
   EvArgs a{};
   for (int i = 0; i < 3; ++i) {
@@ -223,3 +223,35 @@ hipError_t launch_evidential(const float* const head[3], const float* dv, int D,
 }
 
 }  // namespace aarmvs
+
+using namespace aarmvs;
+
+extern "C" {
+
+int aarmvs_evidential_epilogue(const float* const head[3], const float* depth_values, int D, int HW,
+                               float* evidential, float* prob_combine, hipStream_t stream) {
+  if (!head || !head[0] || !head[1] || !head[2] || !depth_values || !evidential || !prob_combine ||
+      HW < 1)
+    return fail(AARMVS_ERR_INVALID, "evidential_epilogue: null pointer or HW < 1");
+  if (D != AARMVS_EVIDENTIAL_D)
+    return fail(AARMVS_ERR_INVALID, "evidential_epilogue: D must be 32 (the head's maxdisp)");
+  return launched(launch_evidential(head, depth_values, D, HW, evidential, prob_combine, nullptr,
+                                    nullptr, nullptr, stream),
+                  "evidential_epilogue");
+}
+
+int aarmvs_evidential_epilogue_backward(const float* const head[3], const float* depth_values, int D,
+                                        int HW, const float* grad_evidential,
+                                        const float* grad_prob_combine, float* const grad_head[3],
+                                        hipStream_t stream) {
+  if (!head || !head[0] || !head[1] || !head[2] || !depth_values || !grad_head || !grad_head[0] ||
+      !grad_head[1] || !grad_head[2] || HW < 1)
+    return fail(AARMVS_ERR_INVALID, "evidential_epilogue_backward: null pointer or HW < 1");
+  if (D != AARMVS_EVIDENTIAL_D)
+    return fail(AARMVS_ERR_INVALID, "evidential_epilogue_backward: D must be 32 (the head's maxdisp)");
+  return launched(launch_evidential(head, depth_values, D, HW, nullptr, nullptr, grad_evidential,
+                                    grad_prob_combine, grad_head, stream),
+                  "evidential_epilogue_backward");
+}
+
+}  // extern "C"

@@ -187,7 +187,7 @@ static void fill_fusion_args(FusionArgs& a, const aarmvs_fusion_args* in) {
   a.depth_avg = in->depth_avg;
 }
 
-hipError_t launch_fusion_filter(const aarmvs_fusion_args* in, hipStream_t s) {
+static hipError_t launch_fusion_filter(const aarmvs_fusion_args* in, hipStream_t s) {
   FusionArgs a{};
   fill_fusion_args(a, in);
   ProfScope ps(s, K_FUSION);
@@ -196,8 +196,8 @@ hipError_t launch_fusion_filter(const aarmvs_fusion_args* in, hipStream_t s) {
 }
 
 // (timed under the plain filter's profile id: the list of kernel names is fixed)
-hipError_t launch_fusion_filter_dedup(const aarmvs_fusion_args* in, const aarmvs_fusion_dedup_args* d,
-                                      hipStream_t s) {
+static hipError_t launch_fusion_filter_dedup(const aarmvs_fusion_args* in, const aarmvs_fusion_dedup_args* d,
+                                             hipStream_t s) {
   FusionDedupArgs a{};
   fill_fusion_args(a, in);
   a.used_ref = d->used_ref;
@@ -260,7 +260,7 @@ __global__ void __launch_bounds__(256) pyr_down_kernel(const float* __restrict__
   }
 }
 
-hipError_t launch_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t s) {
+static hipError_t launch_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t s) {
   const int Ho = (H + 1) / 2, Wo = (W + 1) / 2;
   const dim3 grid((Wo + kPyrTX - 1) / kPyrTX, (Ho + kPyrTY - 1) / kPyrTY);
   if (grid.y > 65535u) return hipErrorInvalidValue;
@@ -416,13 +416,13 @@ static int points_blocks(int H, int W) {
   return (int)(((long long)H * W + kPtsChunk - 1) / kPtsChunk);
 }
 
-size_t fusion_points_workspace_bytes(int H, int W) {
+static size_t fusion_points_workspace_bytes(int H, int W) {
   return ((size_t)points_blocks(H, W) * sizeof(int) + 255) / 256 * 256;
 }
 
 // normal_map == nullptr: the plain write pass (nxyz is not looked at)
-hipError_t launch_fusion_points(const aarmvs_fusion_points_args* in, const float* normal_map, float* nxyz,
-                                hipStream_t s) {
+static hipError_t launch_fusion_points(const aarmvs_fusion_points_args* in, const float* normal_map, float* nxyz,
+                                       hipStream_t s) {
   PointsNormalsArgs a{};
   a.HW = in->H * in->W;
   a.W = in->W;
@@ -562,7 +562,7 @@ __global__ void __launch_bounds__(kNrmThreads) fusion_normals_kernel(NormalsArgs
 }
 
 // (timed under the points' profile id: the list of kernel names is fixed)
-hipError_t launch_fusion_normals(const aarmvs_fusion_normals_args* in, hipStream_t s) {
+static hipError_t launch_fusion_normals(const aarmvs_fusion_normals_args* in, hipStream_t s) {
   NormalsArgs a{};
   a.H = in->H;
   a.W = in->W;
@@ -591,3 +591,108 @@ hipError_t launch_fusion_normals(const aarmvs_fusion_normals_args* in, hipStream
 }
 
 }  // namespace aarmvs
+
+using namespace aarmvs;
+
+extern "C" {
+
+static int fusion_filter_check(const aarmvs_fusion_args* a) {
+  if (!a) return fail(AARMVS_ERR_INVALID, "fusion_filter: null args");
+  if (a->H < 1 || a->W < 1 || a->nsrc < 1 || a->nsrc > AARMVS_MAX_FUSION_SRC)
+    return fail(AARMVS_ERR_INVALID, "fusion_filter: need H, W >= 1 and 1 <= nsrc <= 10");
+  if (!a->ref_depth || !a->confidence || !a->cams || !a->photo_mask || !a->geo_mask ||
+      !a->final_mask || !a->depth_avg)
+    return fail(AARMVS_ERR_INVALID, "fusion_filter: null pointer argument");
+  for (int v = 0; v < a->nsrc; ++v)
+    if (!a->src_depth[v]) return fail(AARMVS_ERR_INVALID, "fusion_filter: null src_depth pointer");
+  return AARMVS_OK;
+}
+
+int aarmvs_fusion_filter(const aarmvs_fusion_args* a, hipStream_t stream) {
+  if (int rc = fusion_filter_check(a)) return rc;
+  return launched(launch_fusion_filter(a, stream), "fusion_filter");
+}
+
+int aarmvs_fusion_filter_dedup(const aarmvs_fusion_args* a, const aarmvs_fusion_dedup_args* d,
+                               hipStream_t stream) {
+  if (!d) return aarmvs_fusion_filter(a, stream);
+  if (int rc = fusion_filter_check(a)) return rc;
+  if (!d->emit_mask) return fail(AARMVS_ERR_INVALID, "fusion_filter_dedup: null emit_mask");
+  if (d->emit_mask == a->photo_mask || d->emit_mask == a->geo_mask || d->emit_mask == a->final_mask)
+    return fail(AARMVS_ERR_INVALID,
+                "fusion_filter_dedup: emit_mask must not be the photo, geo or final mask");
+  // a launch only reads used_ref and only writes the used_src maps: a view is not its own source
+  for (int v = 0; v < a->nsrc; ++v)
+    if (d->used_ref && d->used_src[v] == d->used_ref)
+      return fail(AARMVS_ERR_INVALID, "fusion_filter_dedup: used_ref must not be one of used_src");
+  return launched(launch_fusion_filter_dedup(a, d, stream), "fusion_filter_dedup");
+}
+
+int aarmvs_pyr_down(const float* src, int H, int W, int C, float* dst, hipStream_t stream) {
+  if (!src || !dst) return fail(AARMVS_ERR_INVALID, "pyr_down: null pointer argument");
+  if (H < 4 || W < 4 || (C != 1 && C != 3))
+    return fail(AARMVS_ERR_INVALID, "pyr_down: need H, W >= 4 and C = 1 or 3");
+  if ((long long)H * W * C >= (1LL << 31))
+    return fail(AARMVS_ERR_INVALID, "pyr_down: H * W * C must be below 2^31");
+  return launched(launch_pyr_down(src, H, W, C, dst, stream), "pyr_down");
+}
+
+size_t aarmvs_fusion_points_workspace_bytes(int H, int W) {
+  if (H < 1 || W < 1 || (long long)H * W >= (1LL << 31)) return 0;
+  return fusion_points_workspace_bytes(H, W);
+}
+
+static int fusion_points_check(const aarmvs_fusion_points_args* a) {
+  if (!a) return fail(AARMVS_ERR_INVALID, "fusion_points: null args");
+  if (a->H < 1 || a->W < 1 || (long long)a->H * a->W >= (1LL << 31))
+    return fail(AARMVS_ERR_INVALID, "fusion_points: need H, W >= 1 and H * W < 2^31");
+  if (!a->mask || !a->depth || !a->cams || !a->count || !a->workspace)
+    return fail(AARMVS_ERR_INVALID, "fusion_points: null pointer argument");
+  if (a->capacity < 0) return fail(AARMVS_ERR_INVALID, "fusion_points: negative capacity");
+  if (a->capacity > 0 && !a->xyz)
+    return fail(AARMVS_ERR_INVALID, "fusion_points: null xyz with capacity > 0");
+  if ((a->color == nullptr) != (a->rgb == nullptr))
+    return fail(AARMVS_ERR_INVALID, "fusion_points: color and rgb must both be set or both be null");
+  return AARMVS_OK;
+}
+
+int aarmvs_fusion_points(const aarmvs_fusion_points_args* a, hipStream_t stream) {
+  if (int rc = fusion_points_check(a)) return rc;
+  return launched(launch_fusion_points(a, nullptr, nullptr, stream), "fusion_points");
+}
+
+int aarmvs_fusion_points_normals(const aarmvs_fusion_points_args* a, const float* normal_map, float* nxyz,
+                                 hipStream_t stream) {
+  if (!normal_map && !nxyz) return aarmvs_fusion_points(a, stream);
+  if (int rc = fusion_points_check(a)) return rc;
+  if (!normal_map || !nxyz)
+    return fail(AARMVS_ERR_INVALID,
+                "fusion_points_normals: normal_map and nxyz must both be set or both be null");
+  return launched(launch_fusion_points(a, normal_map, nxyz, stream), "fusion_points_normals");
+}
+
+int aarmvs_fusion_normals(const aarmvs_fusion_normals_args* a, hipStream_t stream) {
+  if (!a) return fail(AARMVS_ERR_INVALID, "fusion_normals: null args");
+  if (a->H < 1 || a->W < 1 || (long long)a->H * a->W >= (1LL << 31))
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: need H, W >= 1 and H * W < 2^31");
+  if (!a->depth || !a->valid || !a->cams || !a->normal)
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: null pointer argument");
+  if (a->radius < 1 || a->radius > AARMVS_MAX_NORMAL_RADIUS)
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: radius must be 1, 2 or 3");
+  const int window = (2 * a->radius + 1) * (2 * a->radius + 1);
+  if (a->min_count < 3 || a->min_count > window)
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: min_count must be in 3 .. (2 radius + 1)^2");
+  if (!(a->max_rel_jump >= 0.0f) || std::isinf(a->max_rel_jump))
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: max_rel_jump must be finite and >= 0");
+  // other blocks still read depth and valid while a block writes its outputs
+  const size_t px = (size_t)a->H * a->W;
+  if (ranges_overlap(a->normal, 12 * px, a->depth, 8 * px) || ranges_overlap(a->normal, 12 * px, a->valid, px))
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: normal must not alias depth or valid");
+  if (a->has_normal &&
+      (ranges_overlap(a->has_normal, px, a->depth, 8 * px) || ranges_overlap(a->has_normal, px, a->valid, px) ||
+       ranges_overlap(a->has_normal, px, a->normal, 12 * px)))
+    return fail(AARMVS_ERR_INVALID, "fusion_normals: has_normal must not alias depth, valid or normal");
+  return launched(launch_fusion_normals(a, stream), "fusion_normals");
+}
+
+}  // extern "C"

@@ -183,13 +183,13 @@ static inline unsigned gn_apply_blocks(int HW) {
   return (unsigned)std::max(1, std::min((HW + kGnThreads - 1) / kGnThreads, 64));
 }
 
-size_t gn_scratch_bytes(int B, int C, int HW) {
+static size_t gn_scratch_bytes(int B, int C, int HW) {
   return (size_t)B * C * gn_nb(HW) * 2 * sizeof(double) + (size_t)B * C * 2 * sizeof(float);
 }
 
-hipError_t launch_group_norm_fwd(const float* x, const float* gamma, const float* beta, int B,
-                                 int C, int HW, int G, float eps, float* y, float* mean_rstd,
-                                 void* scratch, hipStream_t s) {
+static hipError_t launch_group_norm_fwd(const float* x, const float* gamma, const float* beta, int B,
+                                        int C, int HW, int G, float eps, float* y, float* mean_rstd,
+                                        void* scratch, hipStream_t s) {
   const int nb = gn_nb(HW);
   double* part = static_cast<double*>(scratch);
   hipLaunchKernelGGL(gn_fwd_partial_kernel, dim3(nb, C, B), dim3(kGnThreads), 0, s, x, C, HW, part);
@@ -203,9 +203,9 @@ hipError_t launch_group_norm_fwd(const float* x, const float* gamma, const float
   return hipGetLastError();
 }
 
-hipError_t launch_group_norm_bwd(const float* dy, const float* x, const float* gamma,
-                                 const float* mean_rstd, int B, int C, int HW, int G, float* dx,
-                                 float* s1, float* s2, void* scratch, hipStream_t s) {
+static hipError_t launch_group_norm_bwd(const float* dy, const float* x, const float* gamma,
+                                        const float* mean_rstd, int B, int C, int HW, int G, float* dx,
+                                        float* s1, float* s2, void* scratch, hipStream_t s) {
   const int nb = gn_nb(HW);
   double* part = static_cast<double*>(scratch);
   float* coef = reinterpret_cast<float*>(part + (size_t)B * C * nb * 2);
@@ -222,3 +222,33 @@ hipError_t launch_group_norm_bwd(const float* dy, const float* x, const float* g
 }
 
 }  // namespace aarmvs
+
+using namespace aarmvs;
+
+extern "C" {
+
+size_t aarmvs_group_norm_scratch_bytes(int B, int C, int HW) {
+  return (B < 1 || C < 1 || HW < 1) ? 0 : gn_scratch_bytes(B, C, HW);
+}
+
+int aarmvs_group_norm_forward(const float* x, const float* gamma, const float* beta, int B, int C,
+                              int HW, int G, float eps, float* y, float* mean_rstd, void* scratch,
+                              hipStream_t stream) {
+  if (!x || !y || !mean_rstd || !scratch || B < 1 || C < 1 || HW < 1 || G < 1 || C % G != 0 ||
+      B > 65535 || C > 65535)
+    return fail(AARMVS_ERR_INVALID, "group_norm_forward: bad arguments (need G | C)");
+  return launched(launch_group_norm_fwd(x, gamma, beta, B, C, HW, G, eps, y, mean_rstd, scratch, stream),
+                  "group_norm_forward");
+}
+
+int aarmvs_group_norm_backward(const float* dy, const float* x, const float* gamma,
+                               const float* mean_rstd, int B, int C, int HW, int G, float* dx,
+                               float* s1, float* s2, void* scratch, hipStream_t stream) {
+  if (!dy || !x || !mean_rstd || !dx || !s1 || !s2 || !scratch || B < 1 || C < 1 || HW < 1 ||
+      G < 1 || C % G != 0 || B > 65535 || C > 65535)
+    return fail(AARMVS_ERR_INVALID, "group_norm_backward: bad arguments (need G | C)");
+  return launched(launch_group_norm_bwd(dy, x, gamma, mean_rstd, B, C, HW, G, dx, s1, s2, scratch, stream),
+                  "group_norm_backward");
+}
+
+}  // extern "C"

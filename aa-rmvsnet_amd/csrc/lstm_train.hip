@@ -69,17 +69,17 @@ static inline unsigned gates_blocks(size_t n) {
   return (unsigned)std::min<size_t>((n + 255) / 256, 65535);
 }
 
-hipError_t launch_lstm_gates_fwd(const float* z, const float* c_prev, int B, int hid, int HW,
-                                 float* h, float* c, hipStream_t s) {
+static hipError_t launch_lstm_gates_fwd(const float* z, const float* c_prev, int B, int hid, int HW,
+                                        float* h, float* c, hipStream_t s) {
   const size_t n = (size_t)B * hid * HW;
   hipLaunchKernelGGL(lstm_gates_fwd_kernel, dim3(gates_blocks(n)), dim3(256), 0, s, z, c_prev, n,
                      hid, HW, h, c);
   return hipGetLastError();
 }
 
-hipError_t launch_lstm_gates_bwd(const float* z, const float* c_prev, const float* dh,
-                                 const float* dc, int B, int hid, int HW, float* dz, float* dc_prev,
-                                 hipStream_t s) {
+static hipError_t launch_lstm_gates_bwd(const float* z, const float* c_prev, const float* dh,
+                                        const float* dc, int B, int hid, int HW, float* dz, float* dc_prev,
+                                        hipStream_t s) {
   const size_t n = (size_t)B * hid * HW;
   hipLaunchKernelGGL(lstm_gates_bwd_kernel, dim3(gates_blocks(n)), dim3(256), 0, s, z, c_prev, dh,
                      dc, n, hid, HW, dz, dc_prev);
@@ -87,3 +87,24 @@ hipError_t launch_lstm_gates_bwd(const float* z, const float* c_prev, const floa
 }
 
 }  // namespace aarmvs
+
+using namespace aarmvs;
+
+extern "C" {
+
+int aarmvs_lstm_gates_forward(const float* z, const float* c_prev, int B, int hid, int HW, float* h,
+                              float* c, hipStream_t stream) {
+  if (!z || !c_prev || !h || !c || B < 1 || hid < 1 || HW < 1)
+    return fail(AARMVS_ERR_INVALID, "lstm_gates_forward: bad arguments");
+  return launched(launch_lstm_gates_fwd(z, c_prev, B, hid, HW, h, c, stream), "lstm_gates_forward");
+}
+
+int aarmvs_lstm_gates_backward(const float* z, const float* c_prev, const float* dh, const float* dc,
+                               int B, int hid, int HW, float* dz, float* dc_prev, hipStream_t stream) {
+  if (!z || !c_prev || !dz || !dc_prev || B < 1 || hid < 1 || HW < 1)
+    return fail(AARMVS_ERR_INVALID, "lstm_gates_backward: bad arguments");
+  return launched(launch_lstm_gates_bwd(z, c_prev, dh, dc, B, hid, HW, dz, dc_prev, stream),
+                  "lstm_gates_backward");
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 // The sweep's stream schedule, as a host-side description without HIP types: which stream
 // each stage runs on (plan_sweep) and the order of its launches, event records and event waits
-// (walk_sweep).  aarmvs_sweep (api.hip) executes it on HIP; tests/sweep_schedule_check.cpp walks
+// (walk_sweep).  aarmvs_sweep (sweep.hip) executes it on HIP; tests/sweep_schedule_check.cpp walks
 // it with a recording sink and checks, on the CPU, that every pair of conflicting buffer
 // accesses is ordered for every unit -> stream map.
 //

@@ -65,8 +65,8 @@ __global__ void __launch_bounds__(256) homo_warp_kernel(const float* __restrict_
   }
 }
 
-hipError_t launch_homo_warp(const float* src, const float* rel, const float* depth, int B, int C,
-                            int H, int W, float* out, hipStream_t s) {
+static hipError_t launch_homo_warp(const float* src, const float* rel, const float* depth, int B, int C,
+                                   int H, int W, float* out, hipStream_t s) {
   const int HW = H * W;
   dim3 grid((unsigned)std::min((HW + 255) / 256, 4096), (unsigned)B);
   ProfScope ps(s, K_WARP);
@@ -174,12 +174,12 @@ __global__ void __launch_bounds__(256) warp_bwd_fold_kernel(const unsigned long 
 
 constexpr int kWarpBwdChunk = 64;   // batch elements per pass (the 256-B exponent header)
 
-size_t homo_warp_bwd_workspace_bytes(int B, int C, int H, int W) {
+static size_t homo_warp_bwd_workspace_bytes(int B, int C, int H, int W) {
   return 256 + (size_t)std::min(B, kWarpBwdChunk) * C * H * W * 8;
 }
 
-hipError_t launch_homo_warp_bwd(const float* gout, const float* rel, const float* depth, int B,
-                                int C, int H, int W, float* gsrc, void* workspace, hipStream_t s) {
+static hipError_t launch_homo_warp_bwd(const float* gout, const float* rel, const float* depth, int B,
+                                       int C, int H, int W, float* gsrc, void* workspace, hipStream_t s) {
   const int HW = H * W;
   const size_t nb = (size_t)C * HW;
   unsigned* gmax = static_cast<unsigned*>(workspace);
@@ -206,3 +206,33 @@ hipError_t launch_homo_warp_bwd(const float* gout, const float* rel, const float
 }
 
 }  // namespace aarmvs
+
+using namespace aarmvs;
+
+extern "C" {
+
+int aarmvs_homo_warp(const float* src_fea, const float* rel_proj, const float* depth, int B,
+                     int C, int H, int W, float* out, hipStream_t stream) {
+  if (!src_fea || !rel_proj || !depth || !out) return fail(AARMVS_ERR_INVALID, "homo_warp: null pointer");
+  if (B < 1 || C < 1 || H < 2 || W < 2)
+    return fail(AARMVS_ERR_INVALID, "homo_warp: need B>=1, C>=1, H>=2, W>=2");
+  return launched(launch_homo_warp(src_fea, rel_proj, depth, B, C, H, W, out, stream), "homo_warp");
+}
+
+size_t aarmvs_homo_warp_backward_workspace_bytes(int B, int C, int H, int W) {
+  if (B < 1 || C < 1 || H < 2 || W < 2) return 0;
+  return homo_warp_bwd_workspace_bytes(B, C, H, W);
+}
+
+int aarmvs_homo_warp_backward(const float* grad_out, const float* rel_proj, const float* depth,
+                              int B, int C, int H, int W, float* grad_src, void* workspace,
+                              hipStream_t stream) {
+  if (!grad_out || !rel_proj || !depth || !grad_src || !workspace)
+    return fail(AARMVS_ERR_INVALID, "homo_warp_backward: null pointer");
+  if (B < 1 || C < 1 || H < 2 || W < 2)
+    return fail(AARMVS_ERR_INVALID, "homo_warp_backward: need B>=1, C>=1, H>=2, W>=2");
+  return launched(launch_homo_warp_bwd(grad_out, rel_proj, depth, B, C, H, W, grad_src, workspace, stream),
+                  "homo_warp_backward");
+}
+
+}  // extern "C"

@@ -116,7 +116,7 @@ def test_recorded_forward_matches_eval_sweep_and_holds_the_tensors():
                                         ("5", (1, 3, 64, 96, 20)), ("default", (1, 3, 256, 320, 18))])
 def test_recorded_forward_streams_are_bit_identical(monkeypatch, nreg, shape):
     """The training forward's regulariser units on 2, 3 or 5 streams (AARMVS_REG_STREAMS_REC,
-    api.hip reg_unit_streams) against one stream: the cost volume and every record tensor bit
+    sweep_schedule.h plan_sweep, run by sweep.hip) against one stream: the cost volume and every record tensor bit
     for bit, over two plane groups.  64x96 takes the small-frame schedule (cost stage on the
     caller's stream); "default" at 256x320 (> 65536 px) the large-frame one (cost stage on the
     aux stream, units over three streams)."""

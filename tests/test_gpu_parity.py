@@ -388,7 +388,7 @@ def test_sweep_with_points_behind_a_source_camera_matches_oracle():
 @pytest.mark.parametrize("B,N,H,W,D", [(1, 3, 128, 160, 20), (1, 3, 256, 320, 20)])
 def test_sweep_graph_capture_replays_bit_identical(B, N, H, W, D):
     """A caller may record the sweep into a HIP graph (torch.cuda.CUDAGraph): under stream
-    capture the library keeps everything on the capturing stream (api.hip: the multi-stream
+    capture the library keeps everything on the capturing stream (sweep.hip: the multi-stream
     schedules are not captured), and the replay's cost volume and depth equal the eager sweep's
     bit for bit, for a small-frame and a large-frame schedule."""
     from aarmvs import ops

@@ -36,7 +36,9 @@ def _units():
 @pytest.mark.skipif(not os.path.exists(LIB), reason="library not built")
 def test_shipped_code_objects_have_no_packed_fp32_instructions():
     cos = isa.code_objects(LIB)
-    assert len(cos) == len(_units()), "one gfx950 code object per .hip unit"
+    with_kernels = [u for u in _units() if "__global__" in open(os.path.join(CSRC, u)).read()]
+    assert set(_units()) - set(with_kernels) == {"api.hip", "sweep.hip"}, "the host-only units"
+    assert len(cos) == len(with_kernels), "one gfx950 code object per .hip unit that has kernels"
     text = isa.disassemble(LIB)
     assert text.count("v_mfma") > 1000, "the disassembly covers the kernels"
     bad = sorted(set(m.group(0) for m in PACKED.finditer(text)))

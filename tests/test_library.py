@@ -91,6 +91,40 @@ def test_library_calls_run_under_their_tensors_device(monkeypatch):
     assert f(None, x=torch.device("cuda", 1)) == "ran" and entered[-1] == torch.device("cuda", 1)
 
 
+_FAKE = 0x1000   # never dereferenced: validation fails first
+# one rejected call per unit that holds entry points: (function, arguments, its message's prefix)
+_REJECTED = [
+    ("aarmvs_pack_params", (None, _FAKE, None), b"pack_params:"),
+    ("aarmvs_sweep", (None, None), b"sweep: null args"),
+    ("aarmvs_sweep_backward", (None, None), b"sweep_backward:"),
+    ("aarmvs_cost_slice", (_FAKE, None, _FAKE, _FAKE, _FAKE, 1, 8, 8, 8, 1, _FAKE, _FAKE, None, None),
+     b"cost_slice:"),
+    ("aarmvs_unet_step", (_FAKE, 1, 8, 8, 1, -1, _FAKE, _FAKE, _FAKE, None), b"unet_step:"),
+    ("aarmvs_homo_warp", (None, _FAKE, _FAKE, 1, 32, 8, 8, _FAKE, None), b"homo_warp:"),
+    ("aarmvs_softmax_depth", (_FAKE, _FAKE, 1, 0, 64, None), b"softmax_depth:"),
+    ("aarmvs_fusion_filter", (None, None), b"fusion_filter:"),
+    ("aarmvs_group_norm_forward", (None, None, None, 1, 16, 64, 2, 1e-5, _FAKE, _FAKE, _FAKE, None),
+     b"group_norm_forward:"),
+    ("aarmvs_lstm_gates_forward", (None, _FAKE, 1, 8, 64, _FAKE, _FAKE, None), b"lstm_gates_forward:"),
+    ("aarmvs_evidential_epilogue", (None, _FAKE, 32, 64, _FAKE, _FAKE, None), b"evidential_epilogue:"),
+    ("aarmvs_deform_sample", (None, _FAKE, None, 1, 32, 8, 8, 8, 8, 1, 1, _FAKE, None), b"deform_sample:"),
+    ("aarmvs_cls_loss", (None,) + (_FAKE,) * 3 + (1, 4, 64) + (_FAKE,) * 7 + (None,), b"cls_loss:"),
+    ("aarmvs_cloud_keys", (_FAKE, -1, None, 1.0, None, None), b"cloud_keys:"),
+]
+
+
+@pytest.mark.parametrize("name,args,prefix", _REJECTED, ids=[r[0] for r in _REJECTED])
+def test_every_unit_reports_through_the_one_error_string(name, args, prefix):
+    """The entry points sit in their ops' units; the thread's error string is defined in one.  A
+    call rejected in validation (before any device work, so it runs here) leaves its own message
+    in aarmvs_last_error(), whichever unit rejected it and whatever an earlier call left there."""
+    from aarmvs import lib
+    L = lib()
+    assert L.aarmvs_sweep_workspace_bytes(1, 130, 160, 2) == 0 and b"multiple" in L.aarmvs_last_error()
+    assert getattr(L, name)(*args) != 0
+    assert L.aarmvs_last_error().startswith(prefix), L.aarmvs_last_error()
+
+
 def test_deform_sample_rejects_bad_geometry_before_launching():
     """aarmvs_deform_sample validates on the host (no device work, so it runs here): null
     pointers, C other than 32 and non-positive sizes are refused with a message."""

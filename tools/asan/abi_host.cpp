@@ -26,6 +26,11 @@ static bool has_error() {
   return e && std::strlen(e) > 0;
 }
 
+static bool error_is(const char* prefix) {
+  const char* e = aarmvs_last_error();
+  return e && std::strncmp(e, prefix, std::strlen(prefix)) == 0;
+}
+
 // every h / c region of the workspace, written over its full extent
 static void carve(int B, int H, int W, int nsrc) {
   const size_t bytes = aarmvs_sweep_workspace_bytes(B, H, W, nsrc);
@@ -235,6 +240,32 @@ int main() {
         AARMVS_ERR_INVALID);
   CHECK(aarmvs_depth_metrics(dummy, dummy, dummy, 1, 0, thr, 5, ddummy, dummy, nullptr) ==
         AARMVS_ERR_INVALID);
+
+  // The entry points sit in their ops' units, the thread's error string in one (api.hip): after a
+  // rejected call of each unit, aarmvs_last_error() is that call's own message.
+  CHECK(aarmvs_pack_params(nullptr, dummy, nullptr) == AARMVS_ERR_INVALID && error_is("pack_params:"));
+  CHECK(aarmvs_sweep(nullptr, nullptr) == AARMVS_ERR_INVALID && error_is("sweep: null args"));
+  CHECK(aarmvs_sweep_backward(nullptr, nullptr) == AARMVS_ERR_INVALID && error_is("sweep_backward:"));
+  CHECK(aarmvs_cost_slice(dummy, srcs, dummy, dummy, dummy, 1, 8, 8, 8, 1, dummy, dummy, nullptr,
+                          nullptr) == AARMVS_ERR_INVALID && error_is("cost_slice:"));
+  CHECK(aarmvs_unet_step(dummy, 1, 8, 8, 1, -1, dummy, dummy, dummy, nullptr) == AARMVS_ERR_INVALID &&
+        error_is("unet_step:"));
+  CHECK(aarmvs_homo_warp(nullptr, dummy, dummy, 1, 32, 8, 8, dummy, nullptr) == AARMVS_ERR_INVALID &&
+        error_is("homo_warp:"));
+  CHECK(aarmvs_softmax_depth(dummy, dummy, 1, 0, 64, nullptr) == AARMVS_ERR_INVALID && error_is("softmax_depth:"));
+  CHECK(aarmvs_fusion_filter(nullptr, nullptr) == AARMVS_ERR_INVALID && error_is("fusion_filter:"));
+  CHECK(aarmvs_group_norm_forward(nullptr, nullptr, nullptr, 1, 16, 64, 2, 1e-5f, dummy, dummy, dummy,
+                                  nullptr) == AARMVS_ERR_INVALID && error_is("group_norm_forward:"));
+  CHECK(aarmvs_lstm_gates_forward(nullptr, dummy, 1, 8, 64, dummy, dummy, nullptr) == AARMVS_ERR_INVALID &&
+        error_is("lstm_gates_forward:"));
+  CHECK(aarmvs_evidential_epilogue(nullptr, dummy, 32, 64, dummy, dummy, nullptr) == AARMVS_ERR_INVALID &&
+        error_is("evidential_epilogue:"));
+  CHECK(aarmvs_deform_sample(nullptr, dummy, nullptr, 1, 32, 8, 8, 8, 8, 1, 1, dummy, nullptr) ==
+            AARMVS_ERR_INVALID && error_is("deform_sample:"));
+  CHECK(aarmvs_cls_loss(nullptr, dummy, dummy, dummy, 1, 4, 64, dummy, dummy, nullptr, dummy, idummy, dummy,
+                        dummy, nullptr) == AARMVS_ERR_INVALID && error_is("cls_loss:"));
+  CHECK(aarmvs_cloud_keys(dummy, -1, ddummy, 1.0, nullptr, nullptr) == AARMVS_ERR_INVALID &&
+        error_is("cloud_keys:"));
 
   // profiling bookkeeping with nothing recorded
   const int nk = aarmvs_profile_kernel_count();
